@@ -59,13 +59,13 @@ alg = 4096 * 4096 // 2 + 128 * 4096 * 2 + 4096 * 2 + 4096 * 2
 intervals = {"bench_all_headline_launches": interval_view(headline_rows, "every int4g32 1x4096->4096 launch of `bench.py` under rocprofv3 "
                                                           "--kernel-trace: eager warm-up, the timed graphs, the roofline leg's graphs")}
 roofleg = os.path.join(src, "roofleg", "roofleg_kernel_trace.csv")
-if os.path.exists(roofleg):      # the graph-replayed roofline leg alone (bench.py --no-extras --no-cpu-baseline --steps 1440)
+if os.path.exists(roofleg):      # the graph-replayed roofline leg alone (bench.py --full --no-extras --no-cpu-baseline --steps 1440)
     rows = []
     with open(roofleg) as f:
         for r in csv.DictReader(f):
             if "w4_packed_gemv_16_kernel" in r["Kernel_Name"] and int(r["Grid_Size_X"]) == 131072:
                 rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"])))
-    intervals["graph_replayed_roofline_leg"] = interval_view(rows, "bench.py --no-extras --no-cpu-baseline under rocprofv3 --kernel-trace: graph-replayed "
+    intervals["graph_replayed_roofline_leg"] = interval_view(rows, "bench.py --full --no-extras --no-cpu-baseline under rocprofv3 --kernel-trace: graph-replayed "
                                                              "launches only (warm-up excluded by the back-to-back filter)")
     try:
         line = json.loads(open(os.path.join(src, "roofleg.json")).read().strip().split("\n")[-1])
@@ -80,8 +80,8 @@ summary = {
                "in-kernel span.  frac_rocprof in bench.py's line is computed from THIS file, not measured by the driver's run.",
     "methodology_note": "round 5 changed bench.py's headline clock from host perf_counter around the barrier + synchronize bracket to HIP events "
                         "inside it (value 1 479 -> 2 046 GB/s on an unchanged kernel: NOT a speed-up; ADVICE r5).  Round 6 keeps the event clock, "
-                        "reports the wall-clock figure beside it (ms_per_step_wall_clock) and, at --steps < 144, times ceil(1440 / steps) "
-                        "K-step graph replays inside the one bracket and reports the median block (replays, steps_timed).",
+                        "reports the wall-clock figure beside it (ms_per_step_wall_clock); the bracket holds exactly --steps steps, the untimed "
+                        "flush launches queued in front of it so that the graph's start-up is not timed.",
     "pmc": {
         "kernel": "w4_packed_gemv_16_kernel<f16, MB=1, ACH=2, KS=2> on int4g32 1x4096->4096",
         "FETCH_SIZE_KB_per_launch_raw": round(fetch_kb, 1), "WRITE_SIZE_KB_per_launch_raw": round(write_kb, 1),
@@ -91,7 +91,7 @@ summary = {
         "hbm_bytes_per_launch": int(2 * fetch_kb * 1024 + write_kb * 1024),
         "algorithmic_bytes_per_launch": alg,
         "commands": ["tools/profile_round.sh (rocprofv3 --kernel-trace --stats of bench.py; separate --pmc FETCH_SIZE and "
-                     "--pmc WRITE_SIZE passes of bench.py --steps 288 --warmup 72 --no-extras --no-cpu-baseline --launch eager; "
+                     "--pmc WRITE_SIZE passes of bench.py --full --steps 288 --warmup 72 --no-extras --no-cpu-baseline --launch eager; "
                      "kernel traces of tools/profile_decode.py 64 and tools/profile_prefill.py)",
                      "tools/make_profile_summary.py"],
     },

@@ -3,7 +3,7 @@
 # in the Infinity Cache, 72 sets (680 MB) come from HBM.  Output: gpurun_out/mall_sets.txt
 out=gpurun_out/mall_sets.txt; : > $out
 for s in ${@:-2 8 16 24 48 72}; do
-  timeout 150 python bench.py --no-cpu-baseline --sets $s < /dev/null 2>/dev/null | tail -1 > /tmp/line.json
+  timeout 150 python bench.py --full --no-cpu-baseline --sets $s < /dev/null 2>/dev/null | tail -1 > /tmp/line.json
   python - $s >> $out <<'PY'
 import json, sys
 d = json.load(open("/tmp/line.json"))

@@ -7,13 +7,13 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 python $ROOT/bench.py > $OUT/bench_unprofiled.json 2> $OUT/bench_unprofiled.err
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python $ROOT/bench.py --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_rocprof.err
+timeout -k 10 500 python $ROOT/bench.py --full > $OUT/bench_unprofiled.json 2> $OUT/bench_unprofiled.err
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- python $ROOT/bench.py --full --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_rocprof.err
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_$c -o pmc -- python $ROOT/bench.py --steps 288 --warmup 72 --no-extras --no-cpu-baseline --launch eager > $OUT/pmc_$c.json 2> $OUT/pmc_$c.err
+  timeout -k 10 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_$c -o pmc -- python $ROOT/bench.py --full --steps 288 --warmup 72 --no-extras --no-cpu-baseline --launch eager > $OUT/pmc_$c.json 2> $OUT/pmc_$c.err
 done
 # the graph-replayed legs alone (no extras, no CPU baseline): start-to-start intervals of the headline kernel under the profiler
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/roofleg -o roofleg -- python $ROOT/bench.py --no-extras --no-cpu-baseline > $OUT/roofleg.json 2> $OUT/roofleg.err
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/roofleg -o roofleg -- python $ROOT/bench.py --full --no-extras --no-cpu-baseline > $OUT/roofleg.json 2> $OUT/roofleg.err
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/decode -o decode -- python $ROOT/tools/profile_decode.py 64 > $OUT/decode.log 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/decode_sampled -o decode_sampled -- python $ROOT/tools/profile_decode.py 64 sampled > $OUT/decode_sampled.log 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prefill -o prefill -- python $ROOT/tools/profile_prefill.py > $OUT/prefill.log 2>&1
