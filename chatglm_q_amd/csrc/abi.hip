@@ -771,4 +771,14 @@ int qlinear_top_p_sample(const void* logits, int64_t B, int64_t N, int64_t ldl, 
                         capacity, probs_out, index_out, u_out, out_ld, (hipStream_t)stream);
 }
 
+int qlinear_token_logprob(const void* logits, int64_t R, int64_t N, int64_t ldl, const int64_t* targets, int64_t ignore_index,
+                          float* logprob_out, float* lse_out, int64_t* argmax_out, int dtype, void* stream) {
+    if (!dtype_ok(dtype)) return QL_ERR_BAD_DTYPE;
+    if (R < 0 || R >= ((int64_t)1 << 31) || !fits_i32(N) || ldl < N) return QL_ERR_BAD_SHAPE;
+    if (R == 0) return QL_OK;
+    if (!logits || !targets || !logprob_out) return QL_ERR_NULL_POINTER;
+    if (!aligned(logits, (size_t)esize(dtype))) return QL_ERR_MISALIGNED;
+    return token_logprob(dtype, logits, R, N, ldl, targets, ignore_index, logprob_out, lse_out, argmax_out, (hipStream_t)stream);
+}
+
 }  // extern "C"

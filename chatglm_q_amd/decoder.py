@@ -54,6 +54,17 @@ def filtered_distribution(logits: Tensor, top_k: int = 100, top_p: float = 0.8, 
 AHEAD_LAUNCH = True           # greedy graph decoding launches step k + 1 before reading token k (ChatGLMDecoder._generate)
 POST_GENERATE_CHECK = None
 
+class ScoreResult:
+    """What ``DecodeSession.score`` returns.  ``logprobs`` (batch, S - 1) fp32: entry t is log p(labels[:, t + 1] | ids[:, :t + 1]),
+    0 where that label is -100; ``valid`` (batch, S - 1) bool: which entries were scored; ``loss``: 0-dim fp32, minus the mean of
+    the scored entries (the reference's ``F.cross_entropy`` mean, chatglm_q/model.py:388); ``argmax`` (batch, S - 1) int64 or
+    None: the model's own choice at every position; ``logits`` (batch, vocab): the last position's, as ``prefill`` returns them."""
+    __slots__ = ("logprobs", "valid", "loss", "argmax", "logits")
+
+    def __init__(self, logprobs: Tensor, valid: Tensor, loss: Tensor, argmax: Optional[Tensor], logits: Tensor):
+        self.logprobs, self.valid, self.loss, self.argmax, self.logits = logprobs, valid, loss, argmax, logits
+
+
 class DecodeSession:
     """One sequence batch on one device: preallocated cache, eager (chunked) prefill, graph-replayed decode."""
 
@@ -118,6 +129,12 @@ class DecodeSession:
         (``causal | ~attention_mask``) and a token's rotary position is its count among the real tokens
         (``cumsum(attention_mask)``: 1-based, pads get 0).  The pad columns stay masked through later chunks and
         decode steps."""
+        return self._prefill(ids, chunk, attention_mask, None)
+
+    def _prefill(self, ids: Tensor, chunk: Optional[int], attention_mask: Optional[Tensor], per_chunk) -> Tensor:
+        """The chunked loop behind ``prefill`` and ``score``.  ``per_chunk`` None: lm_head runs for every chunk's last position
+        only.  Otherwise every chunk's hidden states in front of ``final_ln`` go to ``per_chunk(s0, s1, hidden)`` and the last
+        position's logits are formed from the final chunk's."""
         B, S = ids.shape
         if S + self.length > self.capacity:
             raise ValueError(f"sequence {S + self.length} exceeds the cache capacity {self.capacity}")
@@ -141,8 +158,17 @@ class DecodeSession:
             rows = torch.arange(self.length + s0, self.length + s1, device=self.device)
             blocked = (t[None, None, :] > rows[None, :, None]) | self.pad_cols[:, None, :]
             mask = blocked.float() * -1e10
-            logits = self.model.step(ids[:, s0:s1], self.cache, rows, positions[:, s0:s1], mask,
-                                     last_only=True, kv_len=self.length + s1)
+            if per_chunk is None:
+                logits = self.model.step(ids[:, s0:s1], self.cache, rows, positions[:, s0:s1], mask,
+                                         last_only=True, kv_len=self.length + s1)
+            else:
+                hidden = self.model.step(ids[:, s0:s1], self.cache, rows, positions[:, s0:s1], mask,
+                                         kv_len=self.length + s1, return_hidden=True)
+                del mask, blocked
+                per_chunk(s0, s1, hidden)
+                if s1 == S:
+                    logits = self.model.head(hidden[:, -1:])
+                del hidden
         self.length += S
         self.cache.length = self.length
         self.n_tokens += valid.long().sum(dim=1)
@@ -155,6 +181,77 @@ class DecodeSession:
         if self.low_footprint:
             self.drop_canonical()                               # the layouts this prefill read exist now: the canonical copies can go
         return logits[:, -1]
+
+    # -- scoring -------------------------------------------------------------------------------------
+    def default_head_rows(self) -> int:
+        """Rows of logits ``score`` holds at a time when not told otherwise: a block of at most 256 MiB, at most 2048 rows
+        (2048 rows at vocabulary 65024 in a 16-bit dtype)."""
+        row_bytes = self.model.config.vocab_size * torch.empty((), dtype=self.dtype).element_size()
+        return max(1, min(2048, (256 << 20) // row_bytes))
+
+    @torch.no_grad()
+    def score(self, ids: Tensor, attention_mask: Optional[Tensor] = None, labels: Optional[Tensor] = None,
+              chunk: Optional[int] = None, head_rows: Optional[int] = None, return_argmax: bool = False) -> "ScoreResult":
+        """Per-token log-probabilities of given ids on the prefill path: the reference's ``forward(labels=...)``
+        (chatglm_q/model.py:384-390) and its perplexity run (examples/evaluations/ppl.py) without ever holding the
+        (batch, S, vocab) logits.  ids (batch, S), ``attention_mask`` as in ``prefill`` (left padding).  ``labels`` (batch, S)
+        follow the reference's convention - same alignment as ids, no shift, -100 = not scored - and default to ``ids`` with
+        -100 at the pad positions (the reference tokenizer's ``return_labels``, chatglm_q/tokenizer.py:138-142): position t
+        is scored against ``labels[:, t + 1]``.
+
+        The same chunked loop as ``prefill`` (``chunk``); per chunk, ``final_ln`` + ``lm_head`` run over blocks of at most
+        ``head_rows`` rows (default: ``default_head_rows()``) and each block of logits goes through one
+        ``fused_ops.token_logprob`` launch and is dropped.  Nothing in the loop waits for the device.  Afterwards the session is
+        armed exactly as after ``prefill(ids)``: ``decode_step`` continues the sequences, ``ScoreResult.logits`` are the last
+        position's logits as ``prefill`` returns them.
+
+        An entry whose QUERY position is a pad - with the default labels, the one in front of a padded row's first token - is
+        scored as the reference scores it, from a position whose attention row is masked everywhere and therefore averages every
+        key of the forward pass: it equals the reference's one-pass ``forward`` when the ids go through in one chunk and moves
+        with ``chunk`` (as the reference's own forward with ``past_key_values`` does).  Every other entry is a function of its
+        sequence alone.  ``ChatGLMDecoder.score_ids`` leaves those entries out unless asked."""
+        from . import fused_ops
+        B, S = ids.shape
+        dev = self.device
+        if labels is None:
+            labels = ids.to(dev)
+            if attention_mask is not None:
+                labels = torch.where(attention_mask.to(dev).bool(), labels, torch.full_like(labels, -100))
+        else:
+            if labels.shape != ids.shape:
+                raise ValueError(f"labels {tuple(labels.shape)} != ids {tuple(ids.shape)}")
+            labels = labels.to(dev)
+        if labels.dtype != torch.int64:
+            labels = labels.long()
+        head_rows = int(head_rows) if head_rows else self.default_head_rows()
+        if head_rows < 1:
+            raise ValueError("head_rows must be positive")
+        # position t's target is labels[:, t + 1]; the last position has none (known up front: chunk / block boundaries need no care)
+        targets = torch.cat((labels[:, 1:], torch.full((B, 1), -100, dtype=torch.int64, device=dev)), dim=1)
+        logprobs = torch.zeros(B, S, dtype=torch.float32, device=dev)
+        argmax = torch.zeros(B, S, dtype=torch.int64, device=dev) if return_argmax else None
+
+        def per_chunk(s0, s1, hidden):
+            h2 = hidden.reshape(B * (s1 - s0), hidden.shape[-1])           # row b * (s1 - s0) + (t - s0)
+            tg = targets[:, s0:s1].reshape(-1)
+            lps, ams = [], []
+            for r0 in range(0, h2.shape[0], head_rows):
+                block = self.model.head(h2[r0:r0 + head_rows])               # (rows, vocab): the only logits alive
+                out = fused_ops.token_logprob(block, tg[r0:r0 + head_rows], -100, return_argmax=return_argmax)
+                del block
+                if return_argmax:
+                    lps.append(out[0]); ams.append(out[1])
+                else:
+                    lps.append(out)
+            logprobs[:, s0:s1] = torch.cat(lps).view(B, s1 - s0)
+            if return_argmax:
+                argmax[:, s0:s1] = torch.cat(ams).view(B, s1 - s0)
+
+        last = self._prefill(ids, chunk, attention_mask, per_chunk)
+        valid = targets[:, :-1] != -100
+        lp = logprobs[:, :-1]
+        loss = (-(lp.sum(dtype=torch.float64) / valid.sum())).float()       # F.cross_entropy's mean over the scored targets
+        return ScoreResult(lp, valid, loss, argmax[:, :-1] if return_argmax else None, last)
 
     # -- one decode step -------------------------------------------------------------------------------
     def set_sampling(self, top_k: int = 100, top_p: float = 0.8, temperature: float = 1.0, seed: Optional[int] = None):
@@ -466,11 +563,21 @@ class ChatGLMDecoder:
                           "reference's load_model_and_tokenizer will not open it")
         save_model(path, self.config, self.model, shard=shard, tokenizer_file=tok)
 
-    def _session_for(self, capacity: int, use_graph: Optional[bool]) -> DecodeSession:
-        """One DecodeSession (cache + captured HIP graph) is kept and reused while the requested capacity fits and the
-        model's parameters have not moved; a generation then costs no allocation and no re-capture."""
+    def _session_for(self, capacity: int, use_graph: Optional[bool], batch: int = 1) -> DecodeSession:
+        """One DecodeSession (cache + captured HIP graph) per batch size is kept and reused while the requested capacity fits and
+        the model's parameters have not moved; a generation (batch 1: ``_session``) or a scoring call (``score_ids``: any batch)
+        then costs no allocation and no re-capture."""
         p = self.model.final_ln.weight
         key = (p.device, p.dtype, p.data_ptr(), use_graph)
+        if batch != 1:
+            kept = self.__dict__.setdefault("_batch_sessions", {})
+            sess = kept.get(batch)
+            if sess is not None and sess[0] == key and sess[1].capacity >= capacity and not sess[1].busy:
+                return sess[1].reset()
+            new = DecodeSession(self.model, batch, capacity, use_graph, low_footprint=self.low_footprint)
+            if sess is None or not sess[1].busy:
+                kept[batch] = (key, new)
+            return new
         sess = getattr(self, "_session", None)
         if sess is not None and self._session_key == key and sess.capacity >= capacity and not sess.busy:
             return sess.reset()
@@ -478,6 +585,72 @@ class ChatGLMDecoder:
             return DecodeSession(self.model, 1, capacity, use_graph, low_footprint=self.low_footprint)
         self._session, self._session_key = DecodeSession(self.model, 1, capacity, use_graph, low_footprint=self.low_footprint), key
         return self._session
+
+    # -- scoring (the reference's forward(labels=...) / examples/evaluations/ppl.py on the session path) ------------------
+    @torch.no_grad()
+    def score_ids(self, sequences, labels=None, chunk: Optional[int] = None, head_rows: Optional[int] = None,
+                  pad_id: int = 0, use_graph: Optional[bool] = None, reference_labels: bool = False):
+        """Per-token log-probabilities of a batch of token-id sequences of any lengths: they are LEFT padded with ``pad_id``
+        (the reference tokenizer's padding side), scored by ``DecodeSession.score`` on a session of that batch size (kept and
+        reused like the generation session) and cut back to their own lengths.  ``labels``: one list per sequence, aligned with
+        its ids, -100 = not scored (a prompt span); default: every token after a sequence's first is scored.
+        ``reference_labels=True`` scores the first token of every PADDED sequence as well, from the pad in front of it - what the
+        reference tokenizer's ``return_labels`` (chatglm_q/tokenizer.py:138-142: the ids, -100 at pads) makes its ``forward`` do, so
+        that the loss is the reference's number for the batch; that entry is no function of the sequence (a pad's attention row is
+        masked everywhere: it averages every key of the pass, so it moves with the batch's width and with ``chunk``) and is not
+        part of the returned lists.  Returns
+        ``(logprobs, loss)``: ``logprobs[b][t]`` = log p(sequences[b][t + 1] | sequences[b][:t + 1]) (``len - 1`` floats, 0.0 at
+        unscored labels) and ``loss`` = minus the mean over every scored token of the batch, the reference's ``forward(labels=)``
+        loss (chatglm_q/model.py:384-390)."""
+        seqs = [list(map(int, s)) for s in sequences]
+        if not seqs or any(len(s) == 0 for s in seqs):
+            raise ValueError("score_ids: at least one sequence, none of them empty")
+        if labels is not None:
+            labels = [list(map(int, l)) for l in labels]
+            if len(labels) != len(seqs) or any(len(l) != len(s) for l, s in zip(labels, seqs)):
+                raise ValueError("score_ids: labels must match the sequences one to one, length by length")
+        B, S = len(seqs), max(len(s) for s in seqs)
+        limit = min(self.max_sequence_length, self.model.config.max_sequence_length)
+        if S > limit:
+            raise ValueError(f"score_ids: a sequence of {S} tokens exceeds the maximum sequence length {limit}")
+        ids = torch.full((B, S), int(pad_id), dtype=torch.long)
+        attn = torch.zeros(B, S, dtype=torch.long)
+        lab = torch.full((B, S), -100, dtype=torch.long)
+        for b, s in enumerate(seqs):
+            ids[b, S - len(s):] = torch.tensor(s, dtype=torch.long)
+            attn[b, S - len(s):] = 1
+            lab[b, S - len(s):] = torch.tensor(labels[b] if labels is not None else s, dtype=torch.long)
+            if not reference_labels:
+                lab[b, S - len(s)] = -100                       # nothing in front of a sequence's first token but padding
+        capacity = min(-(-S // 64) * 64, self.model.config.max_sequence_length)
+        sess = self._session_for(capacity, use_graph, batch=B)
+        sess.busy = True
+        try:
+            res = sess.score(ids, attention_mask=attn, labels=lab, chunk=chunk, head_rows=head_rows)
+            rows = res.logprobs.cpu()                           # the call's one wait for the device
+            loss = float(res.loss)
+        finally:
+            sess.busy = False
+        return [rows[b, S - len(s):].tolist() for b, s in enumerate(seqs)], loss
+
+    def perplexity(self, batches, **kw) -> float:
+        """``exp(mean of the per-batch losses)`` over an iterable of batches (each a list of token-id sequences, scored by
+        ``score_ids``) - the definition of the reference's perplexity run (examples/evaluations/ppl.py:31-45: batches of 20
+        left-padded texts, ``loss, _, _ = model(**inputs)``, ``exp(sum(losses) / len(losses))``): a mean of batch means, not a mean
+        over all tokens."""
+        import math
+        losses = [self.score_ids(batch, **kw)[1] for batch in batches]
+        if not losses:
+            raise ValueError("perplexity: no batches")
+        return math.exp(sum(losses) / len(losses))
+
+    def score(self, texts, **kw):
+        """Text interface of ``score_ids`` when a tokenizer (``encode``) was supplied: one text or a list of texts."""
+        if self.tokenizer is None:
+            raise RuntimeError("no tokenizer: use score_ids() with token ids")
+        single = isinstance(texts, str)
+        logprobs, loss = self.score_ids([self.tokenizer.encode(t) for t in ([texts] if single else texts)], **kw)
+        return (logprobs[0] if single else logprobs), loss
 
     @torch.no_grad()
     def generate_ids(self, prefix_ids: Iterable[int], max_generated_tokens: int = 400, top_k: int = 100,

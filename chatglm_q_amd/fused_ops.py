@@ -342,3 +342,46 @@ def top_p_sample(logits: Tensor, tok: Tensor, rng_state: Tensor | None = None, t
     _lib.check(st, "qlinear_top_p_sample")
     if return_distribution:
         return probs, idx, u
+
+
+def token_logprob(logits: Tensor, targets: Tensor, ignore_index: int = -100, return_lse: bool = False, return_argmax: bool = False):
+    """Per-token log-probabilities of given ids - the per-row tail of the reference's loss (chatglm_q/model.py:384-390:
+    ``logits.float()``, then ``F.cross_entropy``) in one launch and one pass over the rows (``qlinear_token_logprob``):
+    ``logprob[r] = log_softmax(logits[r].float())[targets[r]]`` as fp32, 0 where ``targets[r] == ignore_index``, NaN where it is
+    any other value outside [0, N).  logits (R, N) fp16 / bf16 / fp32 with unit column stride (rows may be strided), targets (R,)
+    int64 on the same device.  Returns ``logprob`` (R,), or the tuple ``(logprob[, lse][, argmax])`` with ``return_lse`` (the
+    log-sum-exp of every row, fp32) / ``return_argmax`` (lowest index of every row's maximum, int64).  CPU tensors take the dense
+    formula, as the modules do."""
+    if logits.dim() != 2 or logits.shape[1] < 1:
+        raise ValueError(f"token_logprob: logits must be (R, N) with N >= 1, got {tuple(logits.shape)}")
+    R, N = logits.shape
+    if targets.dtype != torch.int64 or tuple(targets.shape) != (R,):
+        raise ValueError(f"token_logprob: targets must be an int64 tensor of shape ({R},), got {tuple(targets.shape)} {targets.dtype}")
+    if targets.device != logits.device:
+        raise ValueError(f"token_logprob: logits on {logits.device}, targets on {targets.device}")
+    if not logits.is_cuda:
+        x = logits.float()
+        lse = torch.logsumexp(x, dim=-1)
+        inside = (targets >= 0) & (targets < N)
+        picked = torch.log_softmax(x, dim=-1).gather(1, targets.clamp(0, N - 1)[:, None])[:, 0]
+        lp = torch.where(targets == ignore_index, torch.zeros_like(picked),
+                         torch.where(inside, picked, torch.full_like(picked, float("nan"))))
+        amax = x.argmax(dim=-1) if return_argmax else None
+    else:
+        lib = _lib.get_lib()
+        code = _lib.dtype_code(logits.dtype)
+        if logits.stride(1) != 1 or (R > 1 and logits.stride(0) < N):
+            logits = logits.contiguous()
+        targets = targets.contiguous()
+        lp = torch.empty(R, device=logits.device, dtype=torch.float32)
+        lse = torch.empty(R, device=logits.device, dtype=torch.float32) if return_lse else None
+        amax = torch.empty(R, device=logits.device, dtype=torch.int64) if return_argmax else None
+        if R:
+            with torch.cuda.device(logits.device):
+                st = lib.qlinear_token_logprob(logits.data_ptr(), R, N, logits.stride(0) if R > 1 else N, targets.data_ptr(),
+                                               int(ignore_index), lp.data_ptr(), _lib.ptr(lse), _lib.ptr(amax), code,
+                                               _lib.stream_ptr(logits.device))
+            _lib.check(st, "qlinear_token_logprob")
+    if not (return_lse or return_argmax):
+        return lp
+    return (lp,) + ((lse,) if return_lse else ()) + ((amax,) if return_argmax else ())

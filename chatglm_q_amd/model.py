@@ -223,14 +223,16 @@ class ChatGLM2Model(nn.Module):
 
     # -- one pass over `n_new` positions against a preallocated cache ------------------------------
     def step(self, input_ids: Tensor, cache: KVCache, write_index: Tensor, position_ids: Tensor, mask: Tensor,
-             last_only: bool = False, kv_len: Optional[int] = None) -> Tensor:
+             last_only: bool = False, kv_len: Optional[int] = None, return_hidden: bool = False) -> Tensor:
         """Shape-static forward: embeds input_ids (B, S), writes the new keys/values into the cache rows
         `write_index` (S,), attends over the WHOLE cache capacity under the additive `mask` (B, S, capacity)
         and returns logits.  Every argument is a device tensor, so the call can be captured in a HIP graph
         and replayed with new contents.  `last_only` evaluates lm_head for the final position only (the
         decode loop uses nothing else, chatglm_q/decoder.py:85).  `kv_len` (a HOST integer, so not for captured
         steps) promises that every cache row >= kv_len is masked: attention then reads only the first kv_len
-        rows - the same sums, since a masked column's probability is exactly 0 (prefill uses this)."""
+        rows - the same sums, since a masked column's probability is exactly 0 (prefill uses this).  `return_hidden`: the
+        hidden states in front of `final_ln` / `lm_head` (of the last position only with `last_only`) instead of logits -
+        `head()` turns rows of them into logits (DecodeSession.score evaluates lm_head block by block)."""
         h = self.word_embedding(input_ids)
         fused = FUSED_DECODE_OPS and h.is_cuda
         if fused and h.shape[1] == 1:
@@ -238,7 +240,7 @@ class ChatGLM2Model(nn.Module):
         if kv_len is not None:
             mask = mask[..., :kv_len]
         if fused:
-            return self._step_fused(h, cache, write_index, position_ids, mask, last_only, kv_len)
+            return self._step_fused(h, cache, write_index, position_ids, mask, last_only, kv_len, return_hidden)
         cs = self._rotary(position_ids)
         for i, layer in enumerate(self.layers):
             q, k, v = layer.attn.project(layer.attn_ln(h), cs)
@@ -246,11 +248,21 @@ class ChatGLM2Model(nn.Module):
             cache.v[i].index_copy_(1, write_index, v)
             h = h + layer.attn.attend(h.dtype, q, cache.k[i][:, :kv_len], cache.v[i][:, :kv_len], mask)
             h = h + layer.ffn(layer.ffn_ln(h))
-        h = self.final_ln(h[:, -1:] if last_only else h)
-        return self.lm_head(h)
+        h = h[:, -1:] if last_only else h
+        if return_hidden:
+            return h
+        return self.lm_head(self.final_ln(h))
+
+    def head(self, h: Tensor) -> Tensor:
+        """``lm_head(final_ln(h))`` for hidden states from ``step(return_hidden=True)``, any leading shape: the launches the
+        step itself ends with (the fused RMSNorm on a GPU)."""
+        if FUSED_DECODE_OPS and h.is_cuda:
+            from . import fused_ops as F_
+            return self.lm_head(F_.rmsnorm(h, self.final_ln.weight, self.final_ln.eps))
+        return self.lm_head(self.final_ln(h))
 
     def _step_fused(self, h: Tensor, cache: KVCache, write_index: Tensor, position_ids: Tensor, mask: Tensor,
-                    last_only: bool, kv_len: Optional[int] = None) -> Tensor:
+                    last_only: bool, kv_len: Optional[int] = None, return_hidden: bool = False) -> Tensor:
         """Same graph with the small ops around the QLinear calls fused into single HIP launches
         (csrc/decode_ops.hip): RMSNorm; split + rotary + cache write; single-position attention; SiLU * gate."""
         from . import fused_ops as F_
@@ -260,7 +272,7 @@ class ChatGLM2Model(nn.Module):
         if S == 1 and (kv_len is not None or mask.shape[-1] != cache.capacity):
             raise ValueError("one-position steps take the full-capacity mask (B, 1, capacity) and no kv_len")
         mask = mask.contiguous()
-        if B * S == 1 and h.dtype in (torch.float16, torch.bfloat16):
+        if B * S == 1 and h.dtype in (torch.float16, torch.bfloat16) and not return_hidden:
             kind = self._one_row_kind(h.dtype)
             if kind:
                 return self._step_one_row(h, cache, write_index, position_ids, mask, kind)
@@ -346,6 +358,8 @@ class ChatGLM2Model(nn.Module):
                 delta = layer.ffn.w_out(y)
         if last_only:
             h, delta = h[:, -1:], None if delta is None else delta[:, -1:]
+        if return_hidden:                              # the pending residual contribution folded in: round(h + delta), as add_rmsnorm forms it
+            return h if delta is None else h + delta
         out = self._rows_fused(self.lm_head, h, delta, self.final_ln, want_hout=False) if few else None
         if out is not None:
             return out[0]

@@ -45,7 +45,8 @@ extern "C" {
  * qlinear_dispatch_reset / qlinear_dispatch_reload / qlinear_gemm256_serves / qlinear_tiled_dispatch added; the experimental entry points (one-launch MLP pair / persistent MLP
  * engine / W4A8) moved to include/qlinear_hip_dev.h and libqlinear_hip_dev.so. */
 /* 3 (round 6): qlinear_top_p_sample added; round 5's additions (qlinear_w4g32_unpack_gemv, qlinear_dispatch_flags,
- * qlinear_w4g32_packed_dispatch, QL_K code 19 = ROWS16, qlinear_gated_serves weight_bits 88 = int8 x int8) had gone out under 2. */
+ * qlinear_w4g32_packed_dispatch, QL_K code 19 = ROWS16, qlinear_gated_serves weight_bits 88 = int8 x int8) had gone out under 2.
+ * Still 3: qlinear_token_logprob added - purely additive, no existing entry point changed its signature or its meaning. */
 #define QLINEAR_ABI_VERSION 3
 
 /* activation dtypes */
@@ -491,6 +492,18 @@ int qlinear_greedy_advance(const void* logits, int64_t B, int64_t N, int64_t ldl
 int qlinear_top_p_sample(const void* logits, int64_t B, int64_t N, int64_t ldl, int64_t top_k, float top_p, float temperature,
                          const float* dev_params, uint64_t* rng_state, int64_t* tok, int64_t* write_index, int64_t* pos, float* mask,
                          int64_t capacity, float* probs_out, int64_t* index_out, float* u_out, int64_t out_ld, int dtype, void* stream);
+/* The tail of the reference's loss (chatglm_q/model.py:384-390: logits.float(), then F.cross_entropy) and of its perplexity run
+ * (examples/evaluations/ppl.py) per token, in ONE pass over a block of logits rows - no fp32 copy of the logits, no second walk:
+ *   lse[r] = log(sum_j exp(float(x[r][j])))   (fp32, relative to the row maximum)
+ *   logprob_out[r] = float(x[r][targets[r]]) - lse[r];  0 when targets[r] == ignore_index;  NaN when targets[r] is any other value
+ *   outside [0, N) (nothing is read out of bounds);  argmax_out[r] = lowest index of the row maximum.
+ * logits (R, N) in the activation dtype with row stride ldl >= N and unit column stride, aligned to its element size only (rows
+ * need no 16-byte alignment: the unaligned head and the ragged tail of a row are read element by element); any N >= 1; R == 0 is
+ * QL_OK without a launch.  targets (R) int64 device memory.  lse_out / argmax_out are nullable.  One workgroup per row.  -inf entries
+ * count as probability 0; a row of nothing but -inf yields lse = -inf and a NaN log-prob (as log_softmax does); a NaN logit makes
+ * that row's lse and log-prob NaN and is skipped by the maximum search. */
+int qlinear_token_logprob(const void* logits, int64_t R, int64_t N, int64_t ldl, const int64_t* targets, int64_t ignore_index,
+                          float* logprob_out, float* lse_out, int64_t* argmax_out, int dtype, void* stream);
 
 #ifdef __cplusplus
 }
