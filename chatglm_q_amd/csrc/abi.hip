@@ -781,4 +781,22 @@ int qlinear_token_logprob(const void* logits, int64_t R, int64_t N, int64_t ldl,
     return token_logprob(dtype, logits, R, N, ldl, targets, ignore_index, logprob_out, lse_out, argmax_out, (hipStream_t)stream);
 }
 
+int qlinear_batch_sample_advance(const void* logits, int64_t B, int64_t N, int64_t ldl, const float* row_params, uint64_t* row_rng,
+                                 int32_t* row_state, const int32_t* budget, int64_t* out_tokens, int64_t out_ld, int32_t* live,
+                                 int64_t stop_id, int64_t* tok, int64_t* write_index, int64_t* pos, float* mask, int64_t capacity,
+                                 float* probs_out, int64_t* index_out, float* u_out, int64_t dist_ld, int dtype, void* stream) {
+    if (!dtype_ok(dtype)) return QL_ERR_BAD_DTYPE;
+    if (B < 0 || B >= ((int64_t)1 << 31) || !fits_i32(N) || ldl < N || out_ld < 1 || stop_id >= N) return QL_ERR_BAD_SHAPE;
+    if (B == 0) return QL_OK;
+    if (!logits || !row_params || !row_rng || !row_state || !budget || !out_tokens || !live || !tok) return QL_ERR_NULL_POINTER;
+    const bool book = write_index || pos || mask;
+    if (book && !(write_index && pos && mask)) return QL_ERR_NULL_POINTER;
+    if (book && !fits_i32(capacity)) return QL_ERR_BAD_SHAPE;
+    if ((probs_out == nullptr) != (index_out == nullptr)) return QL_ERR_NULL_POINTER;
+    if (probs_out && (dist_ld < (N < 1024 ? N : 1024) || !fits_i32(dist_ld))) return QL_ERR_BAD_SHAPE;
+    if (!aligned(logits, (size_t)esize(dtype))) return QL_ERR_MISALIGNED;
+    return batch_sample_advance(dtype, logits, B, N, ldl, row_params, row_rng, row_state, budget, out_tokens, out_ld, live, stop_id, tok,
+                                write_index, pos, mask, capacity, probs_out, index_out, u_out, dist_ld, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -283,6 +283,12 @@ int top_p_sample(int dtype, const void* logits, int64_t B, int64_t N, int64_t ld
                  const float* dparams, uint64_t* rng_state, int64_t* tok, int64_t* write_index, int64_t* pos, float* mask,
                  int64_t capacity, float* probs_out, int64_t* index_out, float* u_out, int64_t out_ld, hipStream_t st);
 
+// sampler.hip: batched generation step - per-row sampler settings, generators, budgets and stop, tokens recorded on the device
+int batch_sample_advance(int dtype, const void* logits, int64_t B, int64_t N, int64_t ldl, const float* row_params, uint64_t* row_rng,
+                         int32_t* row_state, const int32_t* budget, int64_t* out_tokens, int64_t out_ld, int32_t* live, int64_t stop_id,
+                         int64_t* tok, int64_t* write_index, int64_t* pos, float* mask, int64_t capacity, float* probs_out,
+                         int64_t* index_out, float* u_out, int64_t dist_ld, hipStream_t st);
+
 // logprob.hip: per-token log-probabilities of given ids, one pass over the logits rows (chatglm_q/model.py:384-390)
 int token_logprob(int dtype, const void* logits, int64_t R, int64_t N, int64_t ldl, const int64_t* targets, int64_t ignore_index,
                   float* logprob_out, float* lse_out, int64_t* argmax_out, hipStream_t st);

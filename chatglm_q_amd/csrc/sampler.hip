@@ -20,6 +20,8 @@
 // Rows that defeat the first threshold (sorted logits, most of the row at -inf, huge tie groups: more than 2048 values >= t0) take
 // an exact bisection instead, one walk over the row per step - slow (tens of microseconds) and still exact, ties by lowest index.
 // The bookkeeping of a decode step (token -> tok, pos += 1, write_index += 1, unmask the new position) is greedy_advance_kernel's.
+// batch_sample_advance_kernel (batched generation) runs the same selection per row (select_top_k, draw_sorted) with per-row settings,
+// generators, budgets and stop in device memory, and records every row's tokens there.
 #include "launch.h"
 #include "ql_common.h"
 
@@ -205,34 +207,19 @@ __device__ __forceinline__ void walk_regs(const u32x4 (&raw)[SU], int N, const S
 #define S_STAMP(i) do { } while (0)
 #endif
 
-template <typename T, bool KEEP>
-__global__ __launch_bounds__(SB) void top_p_sample_kernel(const T* __restrict__ logits, int N, int64_t ldl, int top_k_h, float top_p_h,
-                                                          float temperature_h, const float* __restrict__ dparams,
-                                                          unsigned long long* __restrict__ rng, int64_t* __restrict__ tok,
-                                                          int64_t* __restrict__ write_index, int64_t* __restrict__ pos,
-                                                          float* __restrict__ mask, int capacity, float* __restrict__ probs_out,
-                                                          int64_t* __restrict__ index_out, float* __restrict__ u_out, int out_ld) {
-    __shared__ SamplerShared sh;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const T* row = logits + (int64_t)blockIdx.x * ldl;
+// The draw: u = (Philox4x32-10(counter = (ctr, c2, 0), key = seed).x >> 8) / 2^24, in [0, 1)
+__device__ __forceinline__ float philox_uniform(unsigned long long seed, unsigned long long ctr, u32 c2) {
+    const u32 r = philox4x32_10((u32)ctr, (u32)(ctr >> 32), c2, 0u, (u32)seed, (u32)(seed >> 32));
+    return (float)(r >> 8) * 0x1p-24f;
+}
 
-    // What the LAST statements of the launch need from memory - the generator's state, the position counters - is requested by thread 0
-    // NOW: fetched at the end each of these was a global round trip (~1 us) in the launch's tail (the first version's final wave: 2.1 us).
-    unsigned long long seed = 0ull, ctr = 0ull;
-    int64_t pos_old = 0, widx_old = 0;
-    if (tid == 0) {
-        if (rng) { seed = rng[0]; ctr = rng[1 + blockIdx.x]; }
-        if (pos) pos_old = pos[blockIdx.x];
-        if (write_index && blockIdx.x == 0) widx_old = write_index[0];
-    }
-    // parameters: device-resident ones (a captured graph serves any setting) override the launch's
-    int k = top_k_h;
-    float top_p = top_p_h, temperature = temperature_h;
-    if (dparams) { k = (int)dparams[0]; top_p = dparams[1]; temperature = dparams[2]; }
-    k = k < 1 ? 1 : k;
-    k = k > S_KMAX ? S_KMAX : k;
-    k = k > N ? N : k;
-    const Scale sc = {temperature, 1.0f / temperature, temperature != 1.0f};
+// The selection of one row (top_p_sample_kernel, batch_sample_advance_kernel): passes 1 and 2 over the row, the bisection path of the rare
+// rows, the histogram select and the ranking.  The top k (value desc, index asc) of the scaled row land in sh.sx / sh.si; M = the row's
+// maximum, Z = sum exp(x - M).  1 <= k <= min(S_KMAX, N).  Every thread of the workgroup calls it; u_out is read by the trace build only.
+template <typename T, bool KEEP>
+__device__ __forceinline__ void select_top_k(const T* __restrict__ row, int N, int k, const Scale& sc, SamplerShared& sh, float& M_out,
+                                             float& Z_out, [[maybe_unused]] float* u_out) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 
     S_STAMP(0);
     // ---- pass 1: thread maxima -> the row's maximum M and the first threshold t0 --------------------------------------------------
@@ -518,10 +505,19 @@ __global__ __launch_bounds__(SB) void top_p_sample_kernel(const T* __restrict__ 
         }
         __syncthreads();
     }
+    M_out = M;
+    Z_out = Z;
+}
 
-    S_STAMP(5);
-    // ---- one wave: probabilities, cumulative sums, top-p cut, renormalisation, the draw ---------------------------------------------
-    if (wv == 0) {
+// ---- one wave (wave 0): probabilities of the sorted top k that select_top_k left in LDS, cumulative sums, top-p cut, renormalisation and
+// the inverse-CDF pick at the uniform number uni (the same in every lane).  Returns the picked entry's position in the sorted list, in
+// every lane; s_out = the kept (un-normalised) mass.  probs_row / index_row (nullable together): the filtered distribution in sorted order.
+__device__ __forceinline__ int draw_sorted(const SamplerShared& sh, int k, float top_p, float M, float Z, float uni, float* probs_row,
+                                           int64_t* index_row, float& s_out) {
+    constexpr float L2E = 1.4426950408889634f;
+    const float mb = -M * L2E;
+    const int lane = threadIdx.x & 63;
+    {
         const int per = (k + 63) >> 6;                        // lane l owns sorted entries per * l .. per * l + per - 1
         float p[S_KMAX / 64], c[S_KMAX / 64];
         float run = 0.f;
@@ -555,14 +551,6 @@ __global__ __launch_bounds__(SB) void top_p_sample_kernel(const T* __restrict__ 
         }
         const float s = wave_sum(kept);
         nkept = wave_sum_i(nkept);                            // the kept entries are a prefix of the order (cumsum - p does not decrease)
-        // one uniform draw; the row's own counter advances by one per launch
-        float uni = 0.f;
-        if (lane == 0) {
-            if (rng) rng[1 + blockIdx.x] = ctr + 1ull;
-            const u32 r = philox4x32_10((u32)ctr, (u32)(ctr >> 32), blockIdx.x, 0u, (u32)seed, (u32)(seed >> 32));
-            uni = (float)(r >> 8) * 0x1p-24f;
-        }
-        uni = __shfl(uni, 0, 64);
         const float target = uni * s;                         // inverse CDF on the un-normalised kept mass: entry j with cum(j-1) <= u s < cum(j)
         int jstar = 0x7fffffff;
 #pragma unroll
@@ -576,17 +564,66 @@ __global__ __launch_bounds__(SB) void top_p_sample_kernel(const T* __restrict__ 
             jstar = o < jstar ? o : jstar;
         }
         if (jstar >= nkept) jstar = nkept > 0 ? nkept - 1 : 0;   // u s rounded up to the whole mass: the last kept entry
-        if (probs_out) {
+        if (probs_row) {
 #pragma unroll
             for (int i = 0; i < S_KMAX / 64; ++i)
                 if (i < per) {
                     const int j = per * lane + i;
                     if (j < k) {
-                        probs_out[(int64_t)blockIdx.x * out_ld + j] = p[i] / s;
-                        index_out[(int64_t)blockIdx.x * out_ld + j] = sh.si[j];
+                        probs_row[j] = p[i] / s;
+                        index_row[j] = sh.si[j];
                     }
                 }
         }
+        s_out = s;
+        return jstar;
+    }
+}
+
+template <typename T, bool KEEP>
+__global__ __launch_bounds__(SB) void top_p_sample_kernel(const T* __restrict__ logits, int N, int64_t ldl, int top_k_h, float top_p_h,
+                                                          float temperature_h, const float* __restrict__ dparams,
+                                                          unsigned long long* __restrict__ rng, int64_t* __restrict__ tok,
+                                                          int64_t* __restrict__ write_index, int64_t* __restrict__ pos,
+                                                          float* __restrict__ mask, int capacity, float* __restrict__ probs_out,
+                                                          int64_t* __restrict__ index_out, float* __restrict__ u_out, int out_ld) {
+    __shared__ SamplerShared sh;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const T* row = logits + (int64_t)blockIdx.x * ldl;
+
+    // What the LAST statements of the launch need from memory - the generator's state, the position counters - is requested by thread 0
+    // NOW: fetched at the end each of these was a global round trip (~1 us) in the launch's tail (the first version's final wave: 2.1 us).
+    unsigned long long seed = 0ull, ctr = 0ull;
+    int64_t pos_old = 0, widx_old = 0;
+    if (tid == 0) {
+        if (rng) { seed = rng[0]; ctr = rng[1 + blockIdx.x]; }
+        if (pos) pos_old = pos[blockIdx.x];
+        if (write_index && blockIdx.x == 0) widx_old = write_index[0];
+    }
+    // parameters: device-resident ones (a captured graph serves any setting) override the launch's
+    int k = top_k_h;
+    float top_p = top_p_h, temperature = temperature_h;
+    if (dparams) { k = (int)dparams[0]; top_p = dparams[1]; temperature = dparams[2]; }
+    k = k < 1 ? 1 : k;
+    k = k > S_KMAX ? S_KMAX : k;
+    k = k > N ? N : k;
+    const Scale sc = {temperature, 1.0f / temperature, temperature != 1.0f};
+
+    float M, Z;
+    select_top_k<T, KEEP>(row, N, k, sc, sh, M, Z, u_out);
+
+    S_STAMP(5);
+    if (wv == 0) {
+        // one uniform draw; the row's own counter advances by one per launch
+        float uni = 0.f;
+        if (lane == 0) {
+            if (rng) rng[1 + blockIdx.x] = ctr + 1ull;
+            uni = philox_uniform(seed, ctr, blockIdx.x);
+        }
+        uni = __shfl(uni, 0, 64);
+        float s;
+        const int jstar = draw_sorted(sh, k, top_p, M, Z, uni, probs_out ? probs_out + (int64_t)blockIdx.x * out_ld : nullptr,
+                                      probs_out ? index_out + (int64_t)blockIdx.x * out_ld : nullptr, s);
         S_STAMP(6);
         if (lane == 0) {
             if (u_out) u_out[blockIdx.x] = uni;
@@ -599,6 +636,155 @@ __global__ __launch_bounds__(SB) void top_p_sample_kernel(const T* __restrict__ 
                     for (int b = 0; b < (int)gridDim.x; ++b) mask[(int64_t)b * capacity + nw] = 0.f;
             }
         }
+    }
+}
+
+// Batched generation step (qlinear_batch_sample_advance): row b has its own (top_k, top_p, temperature), its own generator (key
+// row_rng[b][0], counter row_rng[b][1]; the row index is not part of the Philox counter), its own token count / flags / budget and its own
+// token list.  A finished row draws nothing and keeps its state; a live row selects exactly as top_p_sample_kernel does (select_top_k,
+// draw_sorted), or with top_k == 1 takes one argmax walk (greedy_advance_kernel's result: lowest index of the maximum); a row without
+// finite positive mass (NaN, all -inf, +inf logits, temperature <= 0 or NaN) takes the argmax walk's token (NaN skipped; 0 when nothing
+// else is left) and is finished and flagged invalid.
+template <typename T>
+__global__ __launch_bounds__(SB) void batch_sample_advance_kernel(const T* __restrict__ logits, int N, int64_t ldl,
+                                                                  const float* __restrict__ row_params, unsigned long long* __restrict__ row_rng,
+                                                                  int* __restrict__ row_state, const int* __restrict__ budget,
+                                                                  int64_t* __restrict__ out_tokens, int64_t out_ld, int* __restrict__ live,
+                                                                  int64_t stop_id, int64_t* __restrict__ tok, int64_t* __restrict__ write_index,
+                                                                  int64_t* __restrict__ pos, float* __restrict__ mask, int capacity,
+                                                                  float* __restrict__ probs_out, int64_t* __restrict__ index_out,
+                                                                  float* __restrict__ u_out, int dist_ld) {
+    __shared__ SamplerShared sh;
+    __shared__ float s_par[3];
+    __shared__ int s_st[3], s_tok, s_nan;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, b = blockIdx.x;
+    const T* row = logits + (int64_t)b * ldl;
+
+    unsigned long long seed = 0ull, ctr = 0ull;
+    int64_t pos_old = 0, widx_old = 0;
+    if (tid == 0) {
+        seed = row_rng[2 * b]; ctr = row_rng[2 * b + 1];
+        if (pos) pos_old = pos[b];
+        if (write_index && b == 0) widx_old = write_index[0];
+        s_st[0] = row_state[2 * b]; s_st[1] = row_state[2 * b + 1]; s_st[2] = budget[b];
+        s_par[0] = row_params[3 * b]; s_par[1] = row_params[3 * b + 1]; s_par[2] = row_params[3 * b + 2];
+        s_nan = 0;
+    }
+    __syncthreads();
+    const int n0 = s_st[0], flags0 = s_st[1], lim = s_st[2];
+    // the decode step's bookkeeping for every row, finished or not (greedy_advance_kernel's); thread 0
+    auto advance = [&]() {
+        if (pos) pos[b] = pos_old + 1;
+        if (write_index && b == 0) {
+            const int64_t nw = widx_old + 1;
+            write_index[0] = nw;
+            if (nw < capacity)
+                for (int r = 0; r < (int)gridDim.x; ++r) mask[(int64_t)r * capacity + nw] = 0.f;
+        }
+    };
+    if (flags0 & 1) {                                        // finished: no draw, state untouched, the fill token keeps the next gather in range
+        if (tid == 0) {
+            tok[b] = stop_id >= 0 ? stop_id : (n0 > 0 && n0 <= out_ld ? out_tokens[(int64_t)b * out_ld + n0 - 1] : 0);
+            advance();
+        }
+        return;
+    }
+    if (n0 >= lim || n0 >= out_ld || n0 < 0) {               // armed without room (budget 0): finished without a draw
+        if (tid == 0) {
+            row_state[2 * b + 1] = flags0 | 1;
+            atomicSub(live, 1);
+            tok[b] = stop_id >= 0 ? stop_id : (n0 > 0 && n0 <= out_ld ? out_tokens[(int64_t)b * out_ld + n0 - 1] : 0);
+            advance();
+        }
+        return;
+    }
+    // parameters: top_k clamped to [1, min(S_KMAX, N)] (NaN: 1); temperature <= 0 or NaN: an invalid row, never divided by
+    const float kf = s_par[0], top_p = s_par[1], temperature = s_par[2];
+    int k = kf >= 1.f ? (kf < (float)S_KMAX ? (int)kf : S_KMAX) : 1;
+    k = k > N ? N : k;
+    bool invalid = !(temperature > 0.f);
+    float uni = 0.f, s = 1.f;
+    int t = 0;
+
+    if (!invalid && k > 1) {                                 // uniform: the sampler's selection and draw
+        const Scale sc = {temperature, 1.0f / temperature, temperature != 1.0f};
+        float M, Z;
+        select_top_k<T, false>(row, N, k, sc, sh, M, Z, nullptr);
+        if (wv == 0) {
+            if (lane == 0) uni = philox_uniform(seed, ctr, 0u);
+            uni = __shfl(uni, 0, 64);
+            const int jstar = draw_sorted(sh, k, top_p, M, Z, uni, probs_out ? probs_out + (int64_t)b * dist_ld : nullptr,
+                                          probs_out ? index_out + (int64_t)b * dist_ld : nullptr, s);
+            if (lane == 0) {                                 // the LDS list is trusted only with a finite positive mass
+                const bool ok = Z > 0.f && Z < INFINITY && s > 0.f && s < INFINITY;
+                const int cand = ok ? sh.si[jstar] : -1;
+                s_tok = (cand >= 0 && cand < N) ? cand : -1;
+            }
+        }
+        __syncthreads();
+        t = s_tok;
+        invalid = t < 0;
+    }
+    if (invalid || k == 1) {                                 // uniform: one argmax walk over the raw logits
+        // per element one compare and two selects, as in greedy_advance_kernel (a thread's chunks come in ascending index order: the
+        // strict > keeps the lowest index of its maximum; the walk pads past N with -inf, which never wins); the NaN test is a lane-mask or
+        float best = -INFINITY;
+        int besti = 0x7fffffff;
+        bool nan = false;
+        const Scale one = {1.f, 1.f, false};
+        walk_row<T, false>(row, N, one, [&](int c, const float (&v)[8]) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                nan |= v[e] != v[e];
+                if (v[e] > best) { best = v[e]; besti = c * 8 + e; }
+            }
+        });
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float ov = __shfl_xor(best, off, 64);
+            const int oi = __shfl_xor(besti, off, 64);
+            if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+        }
+        if (nan) s_nan = 1;                                  // benign race: every writer stores 1
+        if (lane == 0) { sh.wmax[wv] = best; sh.wcnt[wv] = besti; }
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < 16; ++w)                         // every thread: the block's maximum (ties: lowest index)
+            if (sh.wmax[w] > best || (sh.wmax[w] == best && sh.wcnt[w] < besti)) { best = sh.wmax[w]; besti = sh.wcnt[w]; }
+        if (besti == 0x7fffffff) {                           // uniform, rare: nothing above -inf - the lowest non-NaN index (a -inf), or 0
+            int first = 0x7fffffff;
+            walk_row<T, false>(row, N, one, [&](int c, const float (&v)[8]) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if (v[e] == v[e] && c * 8 + e < N && c * 8 + e < first) first = c * 8 + e;
+            });
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) first = min(first, __shfl_xor(first, off, 64));
+            __syncthreads();                                 // everyone has read sh.wcnt above
+            if (lane == 0) sh.wcnt[wv] = first;
+            __syncthreads();
+#pragma unroll
+            for (int w = 0; w < 16; ++w) first = min(first, sh.wcnt[w]);
+            besti = first;
+        }
+        if (tid == 0) {
+            t = (besti >= 0 && besti < N) ? besti : 0;
+            if (!invalid) invalid = s_nan != 0 || !(best > -INFINITY && best < INFINITY);
+            if (u_out) uni = philox_uniform(seed, ctr, 0u);
+            if (probs_out && !invalid) { probs_out[(int64_t)b * dist_ld] = 1.f; index_out[(int64_t)b * dist_ld] = t; }
+        }
+    }
+    if (tid == 0) {                                          // recording, stopping, bookkeeping
+        out_tokens[(int64_t)b * out_ld + n0] = t;
+        const int n = n0 + 1;
+        const bool fin = invalid || (stop_id >= 0 && t == stop_id) || n >= lim || n >= out_ld;
+        row_state[2 * b] = n;
+        row_state[2 * b + 1] = flags0 | (fin ? 1 : 0) | (invalid ? 2 : 0);
+        row_rng[2 * b + 1] = ctr + 1ull;
+        if (fin) atomicSub(live, 1);
+        if (u_out) u_out[b] = uni;
+        tok[b] = t;
+        advance();
     }
 }
 
@@ -629,6 +815,25 @@ int top_p_sample(int dtype, const void* logits, int64_t B, int64_t N, int64_t ld
     case QL_DTYPE_BF16: QL_SAMPLE(__bf16, false); break;
 #endif
 #undef QL_SAMPLE
+    default: return QL_ERR_BAD_DTYPE;
+    }
+    return finish_launch();
+}
+
+int batch_sample_advance(int dtype, const void* logits, int64_t B, int64_t N, int64_t ldl, const float* row_params, uint64_t* row_rng,
+                         int32_t* row_state, const int32_t* budget, int64_t* out_tokens, int64_t out_ld, int32_t* live, int64_t stop_id,
+                         int64_t* tok, int64_t* write_index, int64_t* pos, float* mask, int64_t capacity, float* probs_out,
+                         int64_t* index_out, float* u_out, int64_t dist_ld, hipStream_t st) {
+    if (N > (int64_t)1 << 30) return QL_ERR_UNSUPPORTED;
+    switch (dtype) {
+#define QL_BSA(TT)                                                                                                                  \
+    batch_sample_advance_kernel<TT><<<(unsigned)B, SB, 0, st>>>((const TT*)logits, (int)N, ldl, row_params, (unsigned long long*)row_rng, \
+                                                                row_state, budget, out_tokens, out_ld, live, stop_id, tok, write_index, pos, \
+                                                                mask, (int)capacity, probs_out, index_out, u_out, (int)dist_ld)
+    case QL_DTYPE_F32: QL_BSA(float); break;
+    case QL_DTYPE_F16: QL_BSA(f16); break;
+    case QL_DTYPE_BF16: QL_BSA(__bf16); break;
+#undef QL_BSA
     default: return QL_ERR_BAD_DTYPE;
     }
     return finish_launch();

@@ -104,6 +104,11 @@ class DecodeSession:
         # generator's (seed, per-row draw counter) live in device memory, so one captured graph serves every setting and every seed
         self.sample_params = torch.tensor([100.0, 0.8, 1.0], dtype=torch.float32, device=dev)
         self.rng_state = torch.zeros(1 + batch, dtype=torch.long, device=dev)
+        # the batched generation's per-row state (arm_rows): sampler settings, generators, token counts / flags, budgets, the tokens
+        # themselves and the live-row count, read and updated on the device by the "rows" step
+        from .fused_ops import BatchRows
+        self.rows = BatchRows(batch, capacity, dev)
+        self._rows_stop = None                                  # the stop id the captured "rows" step bakes in
         self.length = 0
         self.busy = False                                       # a generate_ids generator is running on this session
 
@@ -278,9 +283,30 @@ class DecodeSession:
         fused_ops.top_p_sample(lg, self.tok.view(-1), self.rng_state, dev_params=self.sample_params)
         return self.tok.view(-1)
 
-    def _step_body(self, greedy: bool, sample: bool = False):
+    def arm_rows(self, params, seeds, budgets, stop_id: Optional[int] = None):
+        """Arm the batched generation's per-row state (``fused_ops.BatchRows.arm``): one (top_k, top_p, temperature), seed and
+        budget per row, and the stop id (None: none).  The captured "rows" step bakes the stop id in: a different one drops it."""
+        self.rows.arm(params, seeds, budgets, stop_id)
+        if self._rows_stop is not None and self._rows_stop != self.rows.stop_id:
+            self._graphs.pop("rows", None)
+            if self._captured_mode == "rows":
+                self.graph = self._captured_mode = None
+            self._rows_stop = None
+
+    def sample_rows_first(self, logits: Tensor) -> None:
+        """The first token of every row after a prefill, selected and recorded by the batched step's kernel without bookkeeping
+        (prefill armed the step state); ``tok`` holds the next step's input."""
+        from . import fused_ops
+        fused_ops.batch_sample_advance(logits, self.tok.view(-1), self.rows)
+
+    def _step_body(self, greedy: bool, sample: bool = False, rows: bool = False):
         # invariant on entry: mask is 0 for positions <= write_index (the new position may attend to itself)
         logits = self.model.step(self.tok, self.cache, self.write_index, self.pos, self.mask, last_only=True)
+        if rows:                                                # per-row selection, recording, stop + the bookkeeping: one launch;
+            from . import fused_ops                             # the tokens live in rows.out_tokens (self.logits is not touched)
+            fused_ops.batch_sample_advance(logits[:, -1], self.tok.view(-1), self.rows, self.write_index, self.pos.view(-1),
+                                           self.mask)
+            return
         self.logits = logits[:, -1]
         if sample:                                              # the reference's sampler + the bookkeeping: one launch
             from . import fused_ops
@@ -345,22 +371,22 @@ class DecodeSession:
         return tuple(key)
 
     @staticmethod
-    def _mode(greedy: bool, sample: bool) -> str:
-        return "sample" if sample else ("greedy" if greedy else "logits")
+    def _mode(greedy: bool, sample: bool, rows: bool = False) -> str:
+        return "rows" if rows else ("sample" if sample else ("greedy" if greedy else "logits"))
 
     @property
     def _captured_greedy(self):                                 # kept for the developer tools that read it
         return self._captured_mode == "greedy"
 
     @torch.no_grad()
-    def capture(self, greedy: bool = True, sample: bool = False):
+    def capture(self, greedy: bool = True, sample: bool = False, rows: bool = False):
         """Capture one decode step of the mode - "sample": the device sampler picks the next token, "greedy": the argmax does,
-        "logits": the host decides - or keep the captured one while nothing it bakes in has changed.  Graphs of several modes live
+        "rows": the batched generation's per-row kernel does (arm_rows), "logits": the host decides - or keep the captured one while nothing it bakes in has changed.  Graphs of several modes live
         side by side (a decoder that alternates greedy and sampled generations captures each once)."""
         if not self.use_graph:
             return
         from . import _lib
-        mode = self._mode(greedy, sample)
+        mode = self._mode(greedy, sample, rows)
         if self._graphs:
             # cheap test first (a process-wide counter every derived-layout build / drop bumps), the full fingerprint when it moved
             valid = self._graph_epoch == _lib.layout_epoch() and self._graph_versions == self._canonical_versions()
@@ -375,26 +401,29 @@ class DecodeSession:
                 return
         if self.decode_only:
             self.release_prefill_layouts()
-        saved = (self.tok.clone(), self.write_index.clone(), self.pos.clone(), self.mask.clone(), self.rng_state.clone())
+        state = (self.tok, self.write_index, self.pos, self.mask, self.rng_state) + self.rows.tensors()
+        saved = tuple(t.clone() for t in state)
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
-            self._step_body(greedy, sample)                     # warm-up: allocations, lazy repacks
+            self._step_body(greedy, sample, rows)               # warm-up: allocations, lazy repacks
             # the warm-up built what the step reads (e.g. the gate-interleaved copy of w_in): what it made redundant goes now,
             # and the step runs once more so that every pre-bound launch exists before the capture
             if self.decode_only and self.release_prefill_layouts():
-                self._step_body(greedy, sample)
+                self._step_body(greedy, sample, rows)
             if self.low_footprint and self.drop_canonical():
-                self._step_body(greedy, sample)                 # the pre-bound launches re-validate against the stand-in buffers
+                self._step_body(greedy, sample, rows)           # the pre-bound launches re-validate against the stand-in buffers
         torch.cuda.current_stream(self.device).wait_stream(side)
         if self._graphs and self._graph_epoch != _lib.layout_epoch():
             self._graphs.clear()                                # this mode's warm-up rebuilt / dropped a layout the older graphs baked in
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            self._step_body(greedy, sample)
+            self._step_body(greedy, sample, rows)
         # capture ran the body twice on live state: restore (the cache rows it touched get rewritten)
-        for dst, src in zip((self.tok, self.write_index, self.pos, self.mask, self.rng_state), saved):
+        for dst, src in zip(state, saved):
             dst.copy_(src)
+        if rows:
+            self._rows_stop = self.rows.stop_id
         self._graphs[mode] = graph
         self.graph, self._captured_mode = graph, mode
         self._graph_key = self._layout_fingerprint()            # AFTER the warm-up built the lazy layouts
@@ -415,25 +444,26 @@ class DecodeSession:
         return total
 
     @torch.no_grad()
-    def decode_step(self, token: Optional[Tensor] = None, greedy: bool = True, sample: bool = False) -> Tensor:
+    def decode_step(self, token: Optional[Tensor] = None, greedy: bool = True, sample: bool = False, rows: bool = False) -> Tensor:
         """Advance by one token.  `token` (batch, 1) overrides the device-resident next id (needed when the
         host samples).  ``sample``: the device sampler (set_sampling) draws the next id into ``tok``.  Returns this step's
-        last-position logits (batch, vocab)."""
+        last-position logits (batch, vocab).  ``rows``: the batched generation's step (arm_rows): every row selects, records and
+        stops on its own; returns None (the tokens are in ``rows.out_tokens``)."""
         if self.length + 1 > self.capacity:
             raise ValueError("cache capacity exhausted")
         if token is not None:
             self.tok.copy_(token.to(self.device))
-        mode = self._mode(greedy, sample)
+        mode = self._mode(greedy, sample, rows)
         if mode in self._graphs:
             from . import _lib
             if self._graph_epoch != _lib.layout_epoch() or self._captured_mode != mode:   # a derived layout was rebuilt / dropped since
-                self.capture(greedy, sample)                    # the capture: capture() compares the fingerprint and keeps the graphs
+                self.capture(greedy, sample, rows)              # the capture: capture() compares the fingerprint and keeps the graphs
             self.graph.replay()                                 # when only modules of OTHER models / sessions moved (ADVICE r3)
         else:
-            self._step_body(greedy, sample)
+            self._step_body(greedy, sample, rows)
         self.length += 1
         self.cache.length = self.length
-        return self.logits
+        return None if rows else self.logits
 
 
 class SentencePieceIds:
@@ -790,3 +820,147 @@ class ChatGLMDecoder:
         for tok in self.generate_ids(self.tokenizer.encode(prefix_text), **kw):
             ids.append(tok)
             yield self.tokenizer.decode(ids)
+
+    # -- batched generation --------------------------------------------------------------------------------------------------------
+    # Steps replayed between two looks at the live-row count.  The look is a non-blocking copy of 4 + 8 x batch bytes into pinned memory
+    # and an event behind it; the host waits on the PREVIOUS group's event while the device runs the current group, so it never
+    # idles the device, and a finished batch runs at most 2 x BATCH_POLL_EVERY + 1 steps past its last row's end.  Measured
+    # (profiles/batch_generate_ab.txt): at 4 the whole loop runs at 0.995 - 1.000 of the raw greedy replay loop at batch 8 / 32, so
+    # a larger group has nothing to win; an EOS run wasted 6 steps.
+    BATCH_POLL_EVERY = 4
+    SEED_STRIDE = 0x9E3779B97F4A7C15                            # seed=int: row b's seed is (seed + b * SEED_STRIDE) mod 2^63
+
+    @torch.no_grad()
+    def generate_batch_ids(self, prompts, max_generated_tokens=400, top_k=100, top_p=0.8, temperature=1.0, greedy=False,
+                           seed=None, ignore_eos: bool = False, prefill_chunk: Optional[int] = None, use_graph: Optional[bool] = None,
+                           poll_every: Optional[int] = None):
+        """Generate for a batch of prompts (lists of token ids, any lengths: LEFT padded with 0 as ``score_ids`` pads them) in one
+        decode batch; returns one list of generated ids per prompt.  A row that stopped on the end token ends with it, as
+        ``generate_ids`` yields it.
+
+        ``max_generated_tokens``, ``top_k``, ``top_p``, ``temperature`` and ``greedy`` are scalars or one value per prompt; a
+        greedy row is a top_k 1 row.  Defaults are the reference's sampler (chatglm_q/decoder.py:12-27), as in ``generate_ids``.
+        ``seed``: one per prompt (row b's generator key is ``seed[b]``), an int (row 0 gets it, row b ``(seed + b *
+        SEED_STRIDE) mod 2^63``) or None (the seeds come from torch's global generator: ``torch.manual_seed`` makes a run
+        repeatable).  On a GPU every row draws from its own counter-based generator inside the captured step, so a row's tokens
+        do not depend on its batch position, and a batch of one draws what ``generate_ids`` draws with the same seed.
+
+        Budgets: row b may generate ``min(max_generated_tokens[b], limit - S)`` tokens, S = the longest prompt, limit = the maximum
+        sequence length: the rows share one cache write index, so no row can run past the longest prompt's limit.  A row with
+        budget 0 returns [].  Rows stop on the end token (unless ``ignore_eos``) or their budget; finished rows keep riding along
+        (their compute is not skipped) until every row is done.  ``poll_every``: steps replayed between two looks at the live-row
+        count (default BATCH_POLL_EVERY)."""
+        prompts = [list(map(int, p)) for p in prompts]
+        if not prompts or any(len(p) == 0 for p in prompts):
+            raise ValueError("generate_batch_ids: at least one prompt, none of them empty")
+        B = len(prompts)
+
+        def per_row(name, v, conv):
+            if isinstance(v, (list, tuple)):
+                if len(v) != B:
+                    raise ValueError(f"generate_batch_ids: {name} has {len(v)} entries for {B} prompts")
+                return [conv(x) for x in v]
+            return [conv(v)] * B
+
+        wanted = per_row("max_generated_tokens", max_generated_tokens, int)
+        ks, ps = per_row("top_k", top_k, int), per_row("top_p", top_p, float)
+        ts, gr = per_row("temperature", temperature, float), per_row("greedy", greedy, bool)
+        if any(not t > 0 for t in ts):
+            raise ValueError("generate_batch_ids: temperature > 0")
+        if any(k < 1 for k in ks):
+            raise ValueError("generate_batch_ids: top_k >= 1")
+        ks = [1 if g else k for g, k in zip(gr, ks)]
+        from . import fused_ops
+        on_gpu = self.model.final_ln.weight.device.type == "cuda"
+        if on_gpu and any(k > fused_ops.SAMPLER_MAX_TOP_K for k in ks) and self.model.config.vocab_size > fused_ops.SAMPLER_MAX_TOP_K:
+            raise ValueError(f"generate_batch_ids: top_k <= {fused_ops.SAMPLER_MAX_TOP_K} on a GPU (got {max(ks)})")
+        if seed is None:
+            seeds = torch.randint(0, 2 ** 62, (B,)).tolist()
+        elif isinstance(seed, (list, tuple)):
+            seeds = per_row("seed", seed, int)
+        else:
+            seeds = [(int(seed) + b * self.SEED_STRIDE) & 0x7FFFFFFFFFFFFFFF for b in range(B)]
+        poll = self.BATCH_POLL_EVERY if poll_every is None else int(poll_every)
+        if poll < 1:
+            raise ValueError("generate_batch_ids: poll_every >= 1")
+        S = max(len(p) for p in prompts)
+        limit = min(self.max_sequence_length, self.model.config.max_sequence_length)
+        budgets = [max(0, min(w, limit - S)) for w in wanted]
+        if max(budgets) == 0:
+            self.last_stats = {"batch": B, "prefix": [len(p) for p in prompts], "generated": [0] * B, "steps": 0}
+            return [[] for _ in prompts]
+        ids = torch.zeros((B, S), dtype=torch.long)
+        attn = torch.zeros((B, S), dtype=torch.long)
+        for b, p in enumerate(prompts):
+            ids[b, S - len(p):] = torch.tensor(p, dtype=torch.long)
+            attn[b, S - len(p):] = 1
+        capacity = min(-(-(S + max(budgets)) // 64) * 64, self.model.config.max_sequence_length)
+        stop = None if ignore_eos or self.eos_token_id is None else int(self.eos_token_id)
+        sess = self._session_for(capacity, use_graph, batch=B)
+        sess.busy = True
+        try:
+            sess.arm_rows(list(zip(ks, ps, ts)), seeds, budgets, stop)
+            cuda = sess.device.type == "cuda"
+            t0 = time.perf_counter()
+            logits = sess.prefill(ids, prefill_chunk, attention_mask=attn)
+            sess.sample_rows_first(logits)
+            live = int(sess.rows.live.item())                   # the sync that makes the first-token time valid
+            t_first = time.perf_counter() - t0
+            steps, max_steps = 0, max(budgets) - 1
+            if live > 0 and max_steps > 0:
+                sess.capture(greedy=False, rows=True)
+                if cuda:
+                    ring = torch.zeros((2, 1 + 2 * B), dtype=torch.int32).pin_memory()
+                    events = [torch.cuda.Event(), torch.cuda.Event()]
+                g = 0
+                while steps < max_steps:
+                    n = min(poll, max_steps - steps)
+                    for _ in range(n):
+                        sess.decode_step(greedy=False, rows=True)
+                    steps += n
+                    if not cuda:
+                        if int(sess.rows.live[0]) == 0:
+                            break
+                        continue
+                    ring[g & 1, :1].copy_(sess.rows.live, non_blocking=True)
+                    ring[g & 1, 1:].copy_(sess.rows.row_state.view(-1), non_blocking=True)
+                    events[g & 1].record()
+                    # the previous group's count: its event is behind the group the device is running now
+                    if g > 0:
+                        events[(g - 1) & 1].synchronize()
+                        if int(ring[(g - 1) & 1, 0]) == 0:
+                            break
+                    g += 1
+            out = sess.rows.out_tokens.cpu()                    # one copy of the tokens at the end
+            state = sess.rows.row_state.cpu()
+            total = time.perf_counter() - t0
+        finally:
+            sess.busy = False
+        counts = [int(state[b, 0]) for b in range(B)]
+        res = [out[b, :counts[b]].tolist() for b in range(B)]
+        gen = sum(counts)
+        rest = total - t_first
+        self.last_stats = {
+            "batch": B, "prefix": [len(p) for p in prompts], "generated": counts, "steps": steps,
+            "invalid": [b for b in range(B) if int(state[b, 1]) & fused_ops.BatchRows.INVALID],
+            "prefill_s": t_first, "sum_s": total,
+            "gen_tok_per_s": (gen - sum(1 for c in counts if c)) / rest if steps and rest > 0 else float("nan"),
+            "avg_tok_per_s": gen / total if total > 0 else float("nan"),
+        }
+        if self.time_log:
+            s = self.last_stats
+            print("Decoder (batch):")
+            print(f"  len: {B} rows, {max(s['prefix'])}(longest prefix) + {s['generated']}(gen), {s['steps']} steps")
+            print(f" init: {s['prefill_s']:.6f} s")
+            print(f"  sum: {s['sum_s']:.6f} s")
+            print(f"  gen: {s['gen_tok_per_s']:.6f} tok/s")
+            print(f"  avg: {s['avg_tok_per_s']:.6f} tok/s")
+        return res
+
+    def generate_batch(self, prefix_texts, **kw):
+        """Text interface of ``generate_batch_ids`` when a tokenizer (``encode`` / ``decode``) was supplied: one decoded text per
+        prompt."""
+        if self.tokenizer is None:
+            raise RuntimeError("no tokenizer: use generate_batch_ids() with token ids")
+        outs = self.generate_batch_ids([self.tokenizer.encode(t) for t in prefix_texts], **kw)
+        return [self.tokenizer.decode(o) for o in outs]

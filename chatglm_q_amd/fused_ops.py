@@ -385,3 +385,161 @@ def token_logprob(logits: Tensor, targets: Tensor, ignore_index: int = -100, ret
     if not (return_lse or return_argmax):
         return lp
     return (lp,) + ((lse,) if return_lse else ()) + ((amax,) if return_argmax else ())
+
+
+_SEED_MASK = 0x7FFFFFFFFFFFFFFF
+
+
+def batch_rng_state(seeds, device) -> Tensor:
+    """Device generator state of qlinear_batch_sample_advance: int64 (B, 2) = (seed of row b, draw counter 0) - row b's key is
+    ``seeds[b]`` (taken modulo 2^63), whichever batch position it holds."""
+    st = torch.zeros((len(seeds), 2), dtype=torch.int64)
+    for b, s in enumerate(seeds):
+        st[b, 0] = int(s) & _SEED_MASK
+    return st.to(device)
+
+
+class BatchRows:
+    """Per-row generation state of ``batch_sample_advance`` (static device buffers a captured step reads and updates):
+    ``row_params`` (B, 3) float32 = top_k, top_p, temperature; ``row_rng`` (B, 2) int64 = seed, draw counter; ``row_state`` (B, 2)
+    int32 = tokens generated, flags (bit 0 finished, bit 1 invalid logits); ``budget`` (B,) int32; ``out_tokens`` (B, out_ld) int64;
+    ``live`` (1,) int32 = rows not finished; ``stop_id`` (a host int: -1 = none)."""
+    FINISHED, INVALID = 1, 2
+
+    def __init__(self, batch: int, out_ld: int, device):
+        if batch < 1 or out_ld < 1:
+            raise ValueError(f"BatchRows: batch >= 1 and out_ld >= 1 (got {batch}, {out_ld})")
+        self.batch, self.out_ld, self.device = batch, out_ld, torch.device(device)
+        self.row_params = torch.zeros((batch, 3), dtype=torch.float32, device=device)
+        self.row_rng = torch.zeros((batch, 2), dtype=torch.int64, device=device)
+        self.row_state = torch.zeros((batch, 2), dtype=torch.int32, device=device)
+        self.budget = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.out_tokens = torch.zeros((batch, out_ld), dtype=torch.int64, device=device)
+        self.live = torch.zeros(1, dtype=torch.int32, device=device)
+        self.stop_id = -1
+
+    def arm(self, params, seeds, budgets, stop_id: int | None = None):
+        """Set the state for a new generation, in place (the buffers keep their addresses).  ``params``: one (top_k, top_p,
+        temperature) per row; ``seeds`` / ``budgets``: one int per row; ``stop_id`` None / < 0: no stop token.  A row with
+        budget 0 starts finished."""
+        B = self.batch
+        if len(params) != B or len(seeds) != B or len(budgets) != B:
+            raise ValueError(f"BatchRows.arm: params, seeds and budgets need {B} entries each")
+        for k, p, t in params:
+            if not (int(k) >= 1 and float(t) > 0):
+                raise ValueError(f"BatchRows.arm: top_k >= 1 and temperature > 0 per row (got top_k {k}, temperature {t})")
+        if any(int(n) < 0 or int(n) >= 2 ** 31 for n in budgets):
+            raise ValueError("BatchRows.arm: budgets must be in [0, 2^31)")
+        self.row_params.copy_(torch.tensor([[float(k), float(p), float(t)] for k, p, t in params], dtype=torch.float32))
+        self.row_rng.copy_(batch_rng_state(seeds, "cpu"))
+        st = torch.zeros((B, 2), dtype=torch.int32)
+        st[:, 1] = torch.tensor([self.FINISHED if int(n) == 0 else 0 for n in budgets], dtype=torch.int32)
+        self.row_state.copy_(st)
+        self.budget.copy_(torch.tensor([int(n) for n in budgets], dtype=torch.int32))
+        self.live.fill_(sum(1 for n in budgets if int(n) > 0))
+        self.stop_id = -1 if stop_id is None or stop_id < 0 else int(stop_id)
+        return self
+
+    def tensors(self):
+        return (self.row_params, self.row_rng, self.row_state, self.budget, self.out_tokens, self.live)
+
+
+def _batch_sample_advance_host(logits: Tensor, tok: Tensor, rows: BatchRows, write_index, pos, mask):
+    """CPU form of qlinear_batch_sample_advance: the same per-row rules, selection by torch ops - argmax for top_k == 1, the
+    reference's filtered distribution and one multinomial draw from a generator seeded by (seed, counter) of the row otherwise."""
+    from .decoder import filtered_distribution
+    B, N = logits.shape
+    out_ld = rows.out_ld
+    for b in range(B):
+        n, flags = int(rows.row_state[b, 0]), int(rows.row_state[b, 1])
+        if flags & BatchRows.FINISHED:
+            tok[b] = rows.stop_id if rows.stop_id >= 0 else (int(rows.out_tokens[b, n - 1]) if 0 < n <= out_ld else 0)
+            continue
+        if n >= int(rows.budget[b]) or n >= out_ld:
+            rows.row_state[b, 1] = flags | BatchRows.FINISHED
+            rows.live.sub_(1)
+            tok[b] = rows.stop_id if rows.stop_id >= 0 else (int(rows.out_tokens[b, n - 1]) if 0 < n <= out_ld else 0)
+            continue
+        kf, top_p, temperature = (float(v) for v in rows.row_params[b])
+        k = 1 if not kf >= 1 else min(int(kf), SAMPLER_MAX_TOP_K, N)
+        seed, ctr = int(rows.row_rng[b, 0]), int(rows.row_rng[b, 1])
+        x = logits[b].float()
+        invalid = not temperature > 0
+        t = -1
+        if not invalid and k > 1:
+            probs, idx = filtered_distribution(x, k, top_p, temperature)
+            if bool(torch.isfinite(probs).all()) and float(probs.sum()) > 0:
+                g = torch.Generator().manual_seed((seed * 1000003 + ctr) & _SEED_MASK)
+                t = int(idx[torch.multinomial(probs, 1, generator=g)[0]])
+            else:
+                invalid = True
+        if invalid or k == 1:
+            nan = bool(torch.isnan(x).any())
+            xs = torch.where(torch.isnan(x), torch.full_like(x, float("-inf")), x)
+            t = int(xs.argmax())                                 # lowest index of the largest non-NaN value (all NaN: 0)
+            best = float(xs[t])
+            if not invalid:
+                invalid = nan or not (float("-inf") < best < float("inf"))
+        rows.out_tokens[b, n] = t
+        n += 1
+        fin = invalid or (rows.stop_id >= 0 and t == rows.stop_id) or n >= int(rows.budget[b]) or n >= out_ld
+        rows.row_state[b, 0] = n
+        rows.row_state[b, 1] = flags | (BatchRows.FINISHED if fin else 0) | (BatchRows.INVALID if invalid else 0)
+        rows.row_rng[b, 1] = ctr + 1
+        if fin:
+            rows.live.sub_(1)
+        tok[b] = t
+    if write_index is not None:
+        write_index.add_(1)
+        pos.add_(1)
+        mask.index_fill_(-1, torch.clamp(write_index.view(-1), max=mask.shape[-1] - 1), 0.0)
+
+
+def batch_sample_advance(logits: Tensor, tok: Tensor, rows: BatchRows, write_index: Tensor | None = None, pos: Tensor | None = None,
+                         mask: Tensor | None = None, return_distribution: bool = False):
+    """One batched generation step's selection and bookkeeping in one launch (``qlinear_batch_sample_advance``): row b of `logits`
+    (B, N) is selected with its own sampler settings and generator (``rows``: BatchRows), recorded in ``rows.out_tokens`` and
+    stopped on ``rows.stop_id`` or its budget; ``tok`` (B,) int64 gets the next input ids (a finished row: the fill id).  With
+    write_index / pos / mask (all or none) the decode step's bookkeeping is done as ``greedy_advance`` does it.
+    return_distribution: also return (probs (B, k), indices (B, k), u (B,)) with k = min(1024, N), as ``top_p_sample`` does
+    (entries past a row's own top_k are 0).  CPU tensors take the host form (torch ops, the same per-row rules)."""
+    if logits.dim() != 2 or logits.shape[1] < 1:
+        raise ValueError(f"batch_sample_advance: logits must be (B, N) with N >= 1, got {tuple(logits.shape)}")
+    B, N = logits.shape
+    if B != rows.batch:
+        raise ValueError(f"batch_sample_advance: {B} logits rows for a BatchRows of {rows.batch}")
+    if tok.dtype != torch.int64 or tok.numel() != B or not tok.is_contiguous():
+        raise ValueError("batch_sample_advance: tok must be a contiguous int64 tensor of B elements")
+    book = (write_index is not None, pos is not None, mask is not None)
+    if any(book) and not all(book):
+        raise ValueError("batch_sample_advance: write_index, pos and mask go together")
+    if rows.stop_id >= N:
+        raise ValueError(f"batch_sample_advance: stop id {rows.stop_id} outside the vocabulary of {N}")
+    for t in (tok,) + rows.tensors():
+        if t.device != logits.device:
+            raise ValueError(f"batch_sample_advance: logits on {logits.device}, state on {t.device}")
+    if not logits.is_cuda:
+        if return_distribution:
+            raise ValueError("batch_sample_advance: return_distribution needs the GPU kernel")
+        _batch_sample_advance_host(logits, tok.view(-1), rows, write_index, pos, mask)
+        return None
+    lib = _lib.get_lib()
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    k_out = min(SAMPLER_MAX_TOP_K, N)
+    probs = idx = u = None
+    if return_distribution:
+        probs = torch.zeros((B, k_out), device=logits.device, dtype=torch.float32)
+        idx = torch.zeros((B, k_out), device=logits.device, dtype=torch.int64)
+        u = torch.zeros(B, device=logits.device, dtype=torch.float32)
+    with torch.cuda.device(logits.device):
+        st = lib.qlinear_batch_sample_advance(logits.data_ptr(), B, N, logits.stride(0) if B > 1 else N, rows.row_params.data_ptr(),
+                                              rows.row_rng.data_ptr(), rows.row_state.data_ptr(), rows.budget.data_ptr(),
+                                              rows.out_tokens.data_ptr(), rows.out_ld, rows.live.data_ptr(), rows.stop_id,
+                                              tok.data_ptr(), _lib.ptr(write_index), _lib.ptr(pos), _lib.ptr(mask),
+                                              mask.shape[-1] if mask is not None else 0, _lib.ptr(probs), _lib.ptr(idx), _lib.ptr(u),
+                                              k_out, _lib.dtype_code(logits.dtype), _lib.stream_ptr(logits.device))
+    _lib.check(st, "qlinear_batch_sample_advance")
+    if return_distribution:
+        return probs, idx, u
+    return None

@@ -46,7 +46,8 @@ extern "C" {
  * engine / W4A8) moved to include/qlinear_hip_dev.h and libqlinear_hip_dev.so. */
 /* 3 (round 6): qlinear_top_p_sample added; round 5's additions (qlinear_w4g32_unpack_gemv, qlinear_dispatch_flags,
  * qlinear_w4g32_packed_dispatch, QL_K code 19 = ROWS16, qlinear_gated_serves weight_bits 88 = int8 x int8) had gone out under 2.
- * Still 3: qlinear_token_logprob added - purely additive, no existing entry point changed its signature or its meaning. */
+ * Still 3: qlinear_token_logprob added - purely additive, no existing entry point changed its signature or its meaning.
+ * Still 3: qlinear_batch_sample_advance added - purely additive as well. */
 #define QLINEAR_ABI_VERSION 3
 
 /* activation dtypes */
@@ -504,6 +505,29 @@ int qlinear_top_p_sample(const void* logits, int64_t B, int64_t N, int64_t ldl, 
  * that row's lse and log-prob NaN and is skipped by the maximum search. */
 int qlinear_token_logprob(const void* logits, int64_t R, int64_t N, int64_t ldl, const int64_t* targets, int64_t ignore_index,
                           float* logprob_out, float* lse_out, int64_t* argmax_out, int dtype, void* stream);
+/* Batched generation step in one launch behind lm_head, one workgroup per row: per-row sampler settings, per-row generators, per-row
+ * stop and the tokens recorded on the device, so that a captured graph runs many steps with no host read between them.
+ *   row_params (B, 3) float: top_k, top_p, temperature of row b.  top_k is clamped to [1, min(1024, N)] (NaN: 1).
+ *   row_rng (B, 2) uint64: row b's seed, row b's draw counter.  row_state (B, 2) int32: tokens generated so far (n_b); flags
+ *   (bit 0 finished, bit 1 invalid logits).  budget (B) int32: tokens row b may generate.  out_tokens (B, out_ld) int64: row b's
+ *   tokens in order.  live (1) int32: rows not finished.
+ * A finished row draws nothing, keeps its counter, its tokens and its state; tok[b] = stop_id, or (stop_id < 0) its last token
+ * (0 when it has none).  A live row selects t exactly as qlinear_top_p_sample does for one row with the same logits, parameters and
+ * generator state, except that the Philox counter is (ctr_b, 0, 0) with key seed_b (the row index is not part of it: a row draws
+ * the same whichever batch position it holds); top_k == 1 is qlinear_greedy_advance's argmax (lowest index on ties) in one walk.
+ * Then out_tokens[b][n_b] = t, n_b += 1, ctr_b += 1, tok[b] = t; the row finishes when t == stop_id (stop_id >= 0), n_b == budget[b]
+ * or n_b == out_ld, and then decrements live once (a live row armed with n_b >= budget[b] finishes without a draw).  A row without
+ * finite positive mass (NaN or +inf logits, all -inf, temperature <= 0 or NaN - never divided by) takes the lowest index of its
+ * largest non-NaN logit (0 if none), finishes and is flagged invalid: the token written is always in [0, N).
+ * write_index / pos / mask (nullable together): advanced for every row as qlinear_greedy_advance does; null: nothing advanced (the
+ * first token after a prefill).  probs_out / index_out (B, dist_ld) (nullable together, dist_ld >= min(1024, N)) and u_out (B):
+ * as in qlinear_top_p_sample, for live rows.
+ * QL_ERR_BAD_DTYPE; QL_ERR_BAD_SHAPE for ldl < N, out_ld < 1, N < 1 or stop_id >= N; QL_ERR_NULL_POINTER for a missing required
+ * buffer; B == 0 is QL_OK without a launch. */
+int qlinear_batch_sample_advance(const void* logits, int64_t B, int64_t N, int64_t ldl, const float* row_params, uint64_t* row_rng,
+                                 int32_t* row_state, const int32_t* budget, int64_t* out_tokens, int64_t out_ld, int32_t* live,
+                                 int64_t stop_id, int64_t* tok, int64_t* write_index, int64_t* pos, float* mask, int64_t capacity,
+                                 float* probs_out, int64_t* index_out, float* u_out, int64_t dist_ld, int dtype, void* stream);
 
 #ifdef __cplusplus
 }
