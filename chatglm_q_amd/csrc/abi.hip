@@ -799,4 +799,17 @@ int qlinear_batch_sample_advance(const void* logits, int64_t B, int64_t N, int64
                                 write_index, pos, mask, capacity, probs_out, index_out, u_out, dist_ld, (hipStream_t)stream);
 }
 
+int qlinear_logit_penalties(void* logits, int64_t B, int64_t N, int64_t ldl, const float* settings, const int32_t* bias_ids,
+                            const float* bias_vals, const int32_t* bias_len, int64_t bias_cap, int32_t* state, int64_t lds,
+                            const int64_t* tok, const int32_t* row_state, int dtype, void* stream) {
+    if (!dtype_ok(dtype)) return QL_ERR_BAD_DTYPE;
+    if (B < 0 || B > 65535 || !fits_i32(N) || ldl < N || lds < N || bias_cap < 0 || bias_cap > QL_LOGIT_BIAS_MAX) return QL_ERR_BAD_SHAPE;
+    if (B == 0) return QL_OK;
+    if (!logits || !settings || !state) return QL_ERR_NULL_POINTER;
+    if (bias_cap > 0 && !(bias_ids && bias_vals && bias_len)) return QL_ERR_NULL_POINTER;
+    if (!aligned(logits, (size_t)esize(dtype)) || !aligned(state, 4)) return QL_ERR_MISALIGNED;
+    return logit_penalties(dtype, logits, B, N, ldl, settings, bias_ids, bias_vals, bias_len, bias_cap, state, lds, tok, row_state,
+                           (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -293,6 +293,11 @@ int batch_sample_advance(int dtype, const void* logits, int64_t B, int64_t N, in
 int token_logprob(int dtype, const void* logits, int64_t R, int64_t N, int64_t ldl, const int64_t* targets, int64_t ignore_index,
                   float* logprob_out, float* lse_out, int64_t* argmax_out, hipStream_t st);
 
+// logit_penalties.hip: repetition / presence / frequency penalties + sparse logit bias in place, token history kept on the device
+int logit_penalties(int dtype, void* logits, int64_t B, int64_t N, int64_t ldl, const float* settings, const int32_t* bias_ids,
+                    const float* bias_vals, const int32_t* bias_len, int64_t bias_cap, int32_t* state, int64_t lds, const int64_t* tok,
+                    const int32_t* row_state, hipStream_t st);
+
 // prefill_attention.hip: many-position attention in one launch (D = 128, H = 16 G, fp16 / bf16)
 int prefill_attention(int dtype, const void* Q, const void* Kc, const void* Vc, const float* mask, const uint8_t* flags, void* Out,
                       int64_t B, int64_t S, int64_t Tkv, int64_t H, int64_t G, int64_t cap, int64_t ldm, hipStream_t st);

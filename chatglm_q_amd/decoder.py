@@ -98,6 +98,7 @@ class DecodeSession:
         self.logits: Optional[Tensor] = None
         self.graph = None                                       # the captured step of the mode last asked for ...
         self._graphs = {}                                       # ... of every mode captured under the current layouts
+        self._graph_logits = {}                                 # ... and the logits buffer each of them writes (every graph has its own)
         self._captured_mode = None
         self._graph_key = None
         # the device sampler's state (chatglm_q/decoder.py:12-27 inside the captured step): top_k / top_p / temperature and the
@@ -109,6 +110,9 @@ class DecodeSession:
         from .fused_ops import BatchRows
         self.rows = BatchRows(batch, capacity, dev)
         self._rows_stop = None                                  # the stop id the captured "rows" step bakes in
+        # sampling controls (arm_penalties): token history, penalties and logit bias in device memory, read and updated by the
+        # "+pen" steps.  Allocated by the first penalised generation: a session that never uses them holds nothing extra
+        self.pen = None
         self.length = 0
         self.busy = False                                       # a generate_ids generator is running on this session
 
@@ -275,6 +279,43 @@ class DecodeSession:
         return self.device.type == "cuda" and (top_k <= fused_ops.SAMPLER_MAX_TOP_K
                                                or self.model.config.vocab_size <= fused_ops.SAMPLER_MAX_TOP_K)
 
+    def arm_penalties(self, prompts, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None) -> bool:
+        """Arm the sampling controls for a new generation (``fused_ops.PenaltyState.arm``): ``prompts`` = the REAL prompt ids of
+        every row (no pads); each setting is a scalar or one value per row, ``logit_bias`` a dict ``{id: value}`` (or None) or one
+        per row.  Returns whether anything changes a logit; with every setting at its default nothing is armed - and nothing
+        allocated - and the generation takes the unpenalised steps."""
+        from . import fused_ops
+        B = self.batch
+
+        def per_row(name, v):
+            if isinstance(v, (list, tuple)):
+                if len(v) != B:
+                    raise ValueError(f"arm_penalties: {name} has {len(v)} entries for {B} rows")
+                return list(v)
+            return [v] * B
+
+        if len(prompts) != B:
+            raise ValueError(f"arm_penalties: {len(prompts)} prompts for {B} rows")
+        settings = list(zip(per_row("repetition_penalty", repetition_penalty), per_row("presence_penalty", presence_penalty),
+                            per_row("frequency_penalty", frequency_penalty)))
+        biases = per_row("logit_bias", logit_bias)
+        vocab = self.model.config.vocab_size
+        checked = fused_ops.PenaltyState.check(B, vocab, settings, biases)
+        if fused_ops.PenaltyState.neutral(*checked):
+            if self.pen is not None:
+                self.pen.active = False
+            return False
+        if self.pen is None:
+            self.pen = fused_ops.PenaltyState(B, vocab, self.device)
+        self.pen.arm(prompts, settings, biases)
+        return True
+
+    def penalize_first(self, logits: Tensor, rows: bool = False) -> Tensor:
+        """The armed sampling controls applied in place to a prefill's last-position logits (nothing generated yet: no count)."""
+        from . import fused_ops
+        lg = logits if logits.stride(-1) == 1 else logits.contiguous()
+        return fused_ops.logit_penalties(lg, self.pen, None, self.rows.row_state if rows else None)
+
     def sample_first(self, logits: Tensor) -> Tensor:
         """The token after a prefill, drawn by the device sampler from the prefill's last-position logits (no bookkeeping: prefill
         armed the step state).  Returns the (batch,) device tensor; ``tok`` holds it as the next step's input."""
@@ -288,8 +329,10 @@ class DecodeSession:
         budget per row, and the stop id (None: none).  The captured "rows" step bakes the stop id in: a different one drops it."""
         self.rows.arm(params, seeds, budgets, stop_id)
         if self._rows_stop is not None and self._rows_stop != self.rows.stop_id:
-            self._graphs.pop("rows", None)
-            if self._captured_mode == "rows":
+            for mode in ("rows", "rows+pen"):
+                self._graphs.pop(mode, None)
+                self._graph_logits.pop(mode, None)
+            if self._captured_mode in ("rows", "rows+pen"):
                 self.graph = self._captured_mode = None
             self._rows_stop = None
 
@@ -299,9 +342,12 @@ class DecodeSession:
         from . import fused_ops
         fused_ops.batch_sample_advance(logits, self.tok.view(-1), self.rows)
 
-    def _step_body(self, greedy: bool, sample: bool = False, rows: bool = False):
+    def _step_body(self, greedy: bool, sample: bool = False, rows: bool = False, pen: bool = False):
         # invariant on entry: mask is 0 for positions <= write_index (the new position may attend to itself)
         logits = self.model.step(self.tok, self.cache, self.write_index, self.pos, self.mask, last_only=True)
+        if pen and (greedy or sample or rows):                  # count the id this step was fed, adjust the logits in place: one launch
+            from . import fused_ops                             # in front of the selection (the host-sampled mode adjusts what it gets back)
+            fused_ops.logit_penalties(logits[:, -1], self.pen, self.tok.view(-1), self.rows.row_state if rows else None)
         if rows:                                                # per-row selection, recording, stop + the bookkeeping: one launch;
             from . import fused_ops                             # the tokens live in rows.out_tokens (self.logits is not touched)
             fused_ops.batch_sample_advance(logits[:, -1], self.tok.view(-1), self.rows, self.write_index, self.pos.view(-1),
@@ -371,22 +417,28 @@ class DecodeSession:
         return tuple(key)
 
     @staticmethod
-    def _mode(greedy: bool, sample: bool, rows: bool = False) -> str:
-        return "rows" if rows else ("sample" if sample else ("greedy" if greedy else "logits"))
+    def _mode(greedy: bool, sample: bool, rows: bool = False, pen: bool = False) -> str:
+        mode = "rows" if rows else ("sample" if sample else ("greedy" if greedy else "logits"))
+        return mode + "+pen" if pen and mode != "logits" else mode   # "greedy+pen", "sample+pen", "rows+pen": graphs of their own
 
     @property
     def _captured_greedy(self):                                 # kept for the developer tools that read it
         return self._captured_mode == "greedy"
 
     @torch.no_grad()
-    def capture(self, greedy: bool = True, sample: bool = False, rows: bool = False):
+    def capture(self, greedy: bool = True, sample: bool = False, rows: bool = False, pen: bool = False):
         """Capture one decode step of the mode - "sample": the device sampler picks the next token, "greedy": the argmax does,
         "rows": the batched generation's per-row kernel does (arm_rows), "logits": the host decides - or keep the captured one while nothing it bakes in has changed.  Graphs of several modes live
-        side by side (a decoder that alternates greedy and sampled generations captures each once)."""
+        side by side (a decoder that alternates greedy and sampled generations captures each once).  ``pen``: the step with the sampling
+        controls' launch (arm_penalties) between lm_head and the selection - "greedy+pen" / "sample+pen" / "rows+pen", captured
+        next to the plain ones, which stay as they are."""
         if not self.use_graph:
             return
         from . import _lib
-        mode = self._mode(greedy, sample, rows)
+        mode = self._mode(greedy, sample, rows, pen)
+        pen = mode.endswith("+pen")
+        if pen and self.pen is None:
+            raise RuntimeError("capture(pen=True) before arm_penalties")
         if self._graphs:
             # cheap test first (a process-wide counter every derived-layout build / drop bumps), the full fingerprint when it moved
             valid = self._graph_epoch == _lib.layout_epoch() and self._graph_versions == self._canonical_versions()
@@ -395,39 +447,51 @@ class DecodeSession:
                 valid = True
             if not valid:
                 self._graphs.clear()                            # weights / layouts moved under the graphs: re-capture
+                self._graph_logits.clear()
                 self.graph = self._captured_mode = None
             elif mode in self._graphs:
-                self.graph, self._captured_mode = self._graphs[mode], mode   # a reused session keeps its graphs (static addresses)
+                self._bind(mode)                                # a reused session keeps its graphs (static addresses)
                 return
         if self.decode_only:
             self.release_prefill_layouts()
-        state = (self.tok, self.write_index, self.pos, self.mask, self.rng_state) + self.rows.tensors()
+        # (the token counts of the sampling controls included: the warm-up runs must not count tokens)
+        state = (self.tok, self.write_index, self.pos, self.mask, self.rng_state) + self.rows.tensors() + (self.pen.tensors() if pen else ())
         saved = tuple(t.clone() for t in state)
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
-            self._step_body(greedy, sample, rows)               # warm-up: allocations, lazy repacks
+            self._step_body(greedy, sample, rows, pen)          # warm-up: allocations, lazy repacks
             # the warm-up built what the step reads (e.g. the gate-interleaved copy of w_in): what it made redundant goes now,
             # and the step runs once more so that every pre-bound launch exists before the capture
             if self.decode_only and self.release_prefill_layouts():
-                self._step_body(greedy, sample, rows)
+                self._step_body(greedy, sample, rows, pen)
             if self.low_footprint and self.drop_canonical():
-                self._step_body(greedy, sample, rows)           # the pre-bound launches re-validate against the stand-in buffers
+                self._step_body(greedy, sample, rows, pen)      # the pre-bound launches re-validate against the stand-in buffers
         torch.cuda.current_stream(self.device).wait_stream(side)
         if self._graphs and self._graph_epoch != _lib.layout_epoch():
             self._graphs.clear()                                # this mode's warm-up rebuilt / dropped a layout the older graphs baked in
+            self._graph_logits.clear()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            self._step_body(greedy, sample, rows)
+            self._step_body(greedy, sample, rows, pen)
         # capture ran the body twice on live state: restore (the cache rows it touched get rewritten)
         for dst, src in zip(state, saved):
             dst.copy_(src)
         if rows:
             self._rows_stop = self.rows.stop_id
         self._graphs[mode] = graph
+        # every graph writes a logits buffer of its own: kept with the graph and bound again whenever its mode comes back
+        # ("rows" steps do not publish theirs)
+        self._graph_logits[mode] = None if rows else self.logits
         self.graph, self._captured_mode = graph, mode
         self._graph_key = self._layout_fingerprint()            # AFTER the warm-up built the lazy layouts
         self._graph_epoch, self._graph_versions = _lib.layout_epoch(), self._canonical_versions()
+
+    def _bind(self, mode: str):
+        """Make ``mode``'s captured step the current one: its graph and the logits buffer that graph writes."""
+        self.graph, self._captured_mode = self._graphs[mode], mode
+        if self._graph_logits.get(mode) is not None:
+            self.logits = self._graph_logits[mode]
 
     def _canonical_versions(self):
         """Sum of the canonical buffers' version counters: moves on every in-place write autograd's bookkeeping sees
@@ -444,23 +508,27 @@ class DecodeSession:
         return total
 
     @torch.no_grad()
-    def decode_step(self, token: Optional[Tensor] = None, greedy: bool = True, sample: bool = False, rows: bool = False) -> Tensor:
+    def decode_step(self, token: Optional[Tensor] = None, greedy: bool = True, sample: bool = False, rows: bool = False,
+                    pen: bool = False) -> Tensor:
         """Advance by one token.  `token` (batch, 1) overrides the device-resident next id (needed when the
         host samples).  ``sample``: the device sampler (set_sampling) draws the next id into ``tok``.  Returns this step's
         last-position logits (batch, vocab).  ``rows``: the batched generation's step (arm_rows): every row selects, records and
-        stops on its own; returns None (the tokens are in ``rows.out_tokens``)."""
+        stops on its own; returns None (the tokens are in ``rows.out_tokens``).  ``pen``: the armed sampling controls (arm_penalties)
+        count the id fed into the step and adjust the logits in front of the selection; the host-decides mode (neither greedy, sample
+        nor rows) returns the logits as the model gave them - its caller adjusts them (``fused_ops.logit_penalties``)."""
         if self.length + 1 > self.capacity:
             raise ValueError("cache capacity exhausted")
         if token is not None:
             self.tok.copy_(token.to(self.device))
-        mode = self._mode(greedy, sample, rows)
+        mode = self._mode(greedy, sample, rows, pen)
+        pen = mode.endswith("+pen")
         if mode in self._graphs:
             from . import _lib
             if self._graph_epoch != _lib.layout_epoch() or self._captured_mode != mode:   # a derived layout was rebuilt / dropped since
-                self.capture(greedy, sample, rows)              # the capture: capture() compares the fingerprint and keeps the graphs
+                self.capture(greedy, sample, rows, pen)         # the capture: capture() compares the fingerprint and keeps the graphs
             self.graph.replay()                                 # when only modules of OTHER models / sessions moved (ADVICE r3)
         else:
-            self._step_body(greedy, sample, rows)
+            self._step_body(greedy, sample, rows, pen)
         self.length += 1
         self.cache.length = self.length
         return None if rows else self.logits
@@ -686,14 +754,22 @@ class ChatGLMDecoder:
     def generate_ids(self, prefix_ids: Iterable[int], max_generated_tokens: int = 400, top_k: int = 100,
                      top_p: float = 0.8, temperature: float = 1.0, greedy: bool = False, ignore_eos: bool = False,
                      prefill_chunk: Optional[int] = None, use_graph: Optional[bool] = None, sync_every_token: bool = True,
-                     seed: Optional[int] = None, device_sampler: Optional[bool] = None):
+                     seed: Optional[int] = None, device_sampler: Optional[bool] = None, repetition_penalty: float = 1.0,
+                     presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias: Optional[dict] = None):
         """Yields generated token ids one by one (batch 1, like the reference, chatglm_q/decoder.py:70).
 
         Default = the reference's only mode: top-k / top-p sampling (top_k 100, top_p 0.8, temperature 1.0).  On a GPU the
         sampler is one launch inside the captured step (``device_sampler`` None / True; False: the composed torch ops of
         ``top_p_sampling`` on the host's side of the loop, as the reference runs them) and draws from a counter-based generator
         seeded by ``seed`` (None: a seed taken from torch's global generator, so ``torch.manual_seed`` makes a run repeatable as it
-        does for the reference's ``torch.multinomial``).  ``greedy=True``: argmax instead."""
+        does for the reference's ``torch.multinomial``).  ``greedy=True``: argmax instead.
+
+        Sampling controls (defaults: off, the path above exactly): ``repetition_penalty`` r > 0 divides the positive and
+        multiplies the other logits of every id in the prompt or generated so far (the Hugging Face rule); ``presence_penalty`` p
+        and ``frequency_penalty`` f subtract p + f x (times generated) from the logit of every id generated so far (OpenAI's
+        rule); ``logit_bias`` ``{id: value}`` (at most ``fused_ops.LOGIT_BIAS_MAX`` entries, values finite or -inf: -inf bans the
+        id) is added last.  They run as one more launch inside the captured step, in front of the argmax / the sampler, on the
+        history kept on the device; ``last_stats["penalties"]`` says whether they were active."""
         prefix = list(prefix_ids)
         limit = min(self.max_sequence_length, self.model.config.max_sequence_length)   # the cache cannot outgrow the rotary table
         budget = min(max_generated_tokens, limit - len(prefix))
@@ -703,6 +779,7 @@ class ChatGLMDecoder:
         sess = self._session_for(capacity, use_graph)
         sess.busy = True
         try:
+            pen = sess.arm_penalties([prefix], repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
             dev_sample = (not greedy) and sess.device_sampler_serves(top_k) and device_sampler is not False
             if device_sampler and not greedy and not dev_sample:
                 raise ValueError(f"device_sampler=True needs a GPU and top_k <= 1024 (got {sess.device}, top_k {top_k})")
@@ -711,14 +788,14 @@ class ChatGLMDecoder:
                     seed = int(torch.randint(0, 2 ** 62, (1,)).item())
                 sess.set_sampling(top_k, top_p, temperature, seed)
             yield from self._generate(sess, prefix, budget, top_k, top_p, temperature, greedy, ignore_eos, prefill_chunk,
-                                      sync_every_token, dev_sample)
+                                      sync_every_token, dev_sample, pen)
         finally:
             sess.busy = False
             if POST_GENERATE_CHECK is not None:                 # set by chatglm_q_amd.dev.experiments: error words of one-launch MLPs
                 POST_GENERATE_CHECK(sess)
 
     def _generate(self, sess: DecodeSession, prefix, budget: int, top_k: int, top_p: float, temperature: float, greedy: bool,
-                  ignore_eos: bool, prefill_chunk: Optional[int], sync_every_token: bool, dev_sample: bool = False):
+                  ignore_eos: bool, prefill_chunk: Optional[int], sync_every_token: bool, dev_sample: bool = False, pen: bool = False):
         # `auto`: the device picks the next token inside the step (argmax or the one-launch sampler) and feeds it back itself
         auto = greedy or dev_sample
         times = []
@@ -726,6 +803,8 @@ class ChatGLMDecoder:
 
         t0 = time.perf_counter()
         logits = sess.prefill(torch.tensor([prefix], dtype=torch.long), prefill_chunk)
+        if pen:                                                    # nothing generated yet: prompt ids and the bias only
+            logits = sess.penalize_first(logits)
         if dev_sample:
             nxt = sess.sample_first(logits)
         else:
@@ -738,7 +817,7 @@ class ChatGLMDecoder:
         device_loop = auto and not sync_every_token and (ignore_eos or self.eos_token_id is None)
         if len(generated) < budget and (ignore_eos or token != self.eos_token_id):
             sess.tok.fill_(token)
-            sess.capture(greedy=greedy, sample=dev_sample)
+            sess.capture(greedy=greedy, sample=dev_sample, pen=pen)
         pending = []
         # Greedy or device-sampled decoding on a captured step: the graph feeds its own choice back, so step k + 1 does not wait for the HOST to have seen
         # token k.  It is launched before token k is read (one step of speculation: wasted - and harmless, the next prefill re-arms the
@@ -751,7 +830,7 @@ class ChatGLMDecoder:
             events = [torch.cuda.Event(), torch.cuda.Event()]
 
             def launch(k):
-                sess.decode_step(None, greedy=greedy, sample=dev_sample)
+                sess.decode_step(None, greedy=greedy, sample=dev_sample, pen=pen)
                 ring[k & 1].copy_(sess.tok.view(-1), non_blocking=True)
                 events[k & 1].record()
 
@@ -776,12 +855,15 @@ class ChatGLMDecoder:
             t0 = time.perf_counter()
             if device_loop:
                 # the graph feeds its own choice back as the next input: the host only replays
-                sess.decode_step(greedy=greedy, sample=dev_sample)
+                sess.decode_step(greedy=greedy, sample=dev_sample, pen=pen)
                 pending.append(sess.tok.clone())
                 generated.append(-1)
                 times.append(time.perf_counter() - t0)
                 continue
-            logits = sess.decode_step(None if auto else torch.tensor([[generated[-1]]]), greedy=greedy, sample=dev_sample)
+            logits = sess.decode_step(None if auto else torch.tensor([[generated[-1]]]), greedy=greedy, sample=dev_sample, pen=pen)
+            if pen and not auto:                                   # the host samples: it adjusts the logits it got back (tok = the id just fed)
+                from . import fused_ops
+                logits = fused_ops.logit_penalties(logits if logits.stride(-1) == 1 else logits.contiguous(), sess.pen, sess.tok.view(-1))
             nxt = sess.tok[:, 0] if auto else top_p_sampling(logits, top_k, top_p, temperature)
             token = int(nxt.item())
             times.append(time.perf_counter() - t0)
@@ -801,7 +883,7 @@ class ChatGLMDecoder:
         self.last_stats = {
             "prefix": len(prefix), "generated": n, "init_s": times[0], "sum_s": sum(times),
             "gen_tok_per_s": (n - 1) / rest if n > 1 and rest > 0 else float("nan"),
-            "avg_tok_per_s": n / sum(times),
+            "avg_tok_per_s": n / sum(times), "penalties": bool(pen),
         }
         if self.time_log:
             s = self.last_stats
@@ -833,7 +915,8 @@ class ChatGLMDecoder:
     @torch.no_grad()
     def generate_batch_ids(self, prompts, max_generated_tokens=400, top_k=100, top_p=0.8, temperature=1.0, greedy=False,
                            seed=None, ignore_eos: bool = False, prefill_chunk: Optional[int] = None, use_graph: Optional[bool] = None,
-                           poll_every: Optional[int] = None):
+                           poll_every: Optional[int] = None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
+                           logit_bias=None):
         """Generate for a batch of prompts (lists of token ids, any lengths: LEFT padded with 0 as ``score_ids`` pads them) in one
         decode batch; returns one list of generated ids per prompt.  A row that stopped on the end token ends with it, as
         ``generate_ids`` yields it.
@@ -849,7 +932,13 @@ class ChatGLMDecoder:
         sequence length: the rows share one cache write index, so no row can run past the longest prompt's limit.  A row with
         budget 0 returns [].  Rows stop on the end token (unless ``ignore_eos``) or their budget; finished rows keep riding along
         (their compute is not skipped) until every row is done.  ``poll_every``: steps replayed between two looks at the live-row
-        count (default BATCH_POLL_EVERY)."""
+        count (default BATCH_POLL_EVERY).
+
+        ``repetition_penalty``, ``presence_penalty``, ``frequency_penalty`` and ``logit_bias`` (a dict ``{id: value}`` or None) are
+        ``generate_ids``' sampling controls, each a scalar / one dict or one per prompt.  A row's history is its own prompt (the pads
+        in front of it are no prompt tokens) and its own tokens; the controls run as one more launch in the captured step, so a
+        row's tokens still do not depend on its batch position or on its neighbours' settings.  Defaults: off, the path above
+        exactly; ``last_stats["penalties"]`` says whether they were active."""
         prompts = [list(map(int, p)) for p in prompts]
         if not prompts or any(len(p) == 0 for p in prompts):
             raise ValueError("generate_batch_ids: at least one prompt, none of them empty")
@@ -886,8 +975,12 @@ class ChatGLMDecoder:
         S = max(len(p) for p in prompts)
         limit = min(self.max_sequence_length, self.model.config.max_sequence_length)
         budgets = [max(0, min(w, limit - S)) for w in wanted]
+        # (validated up front: wrong lengths / values raise before anything runs)
+        pen_args = (per_row("repetition_penalty", repetition_penalty, float), per_row("presence_penalty", presence_penalty, float),
+                    per_row("frequency_penalty", frequency_penalty, float), per_row("logit_bias", logit_bias, lambda d: d))
+        fused_ops.PenaltyState.check(B, self.model.config.vocab_size, list(zip(*pen_args[:3])), pen_args[3])
         if max(budgets) == 0:
-            self.last_stats = {"batch": B, "prefix": [len(p) for p in prompts], "generated": [0] * B, "steps": 0}
+            self.last_stats = {"batch": B, "prefix": [len(p) for p in prompts], "generated": [0] * B, "steps": 0, "penalties": False}
             return [[] for _ in prompts]
         ids = torch.zeros((B, S), dtype=torch.long)
         attn = torch.zeros((B, S), dtype=torch.long)
@@ -900,15 +993,18 @@ class ChatGLMDecoder:
         sess.busy = True
         try:
             sess.arm_rows(list(zip(ks, ps, ts)), seeds, budgets, stop)
+            pen = sess.arm_penalties(prompts, *pen_args)
             cuda = sess.device.type == "cuda"
             t0 = time.perf_counter()
             logits = sess.prefill(ids, prefill_chunk, attention_mask=attn)
+            if pen:
+                logits = sess.penalize_first(logits, rows=True)
             sess.sample_rows_first(logits)
             live = int(sess.rows.live.item())                   # the sync that makes the first-token time valid
             t_first = time.perf_counter() - t0
             steps, max_steps = 0, max(budgets) - 1
             if live > 0 and max_steps > 0:
-                sess.capture(greedy=False, rows=True)
+                sess.capture(greedy=False, rows=True, pen=pen)
                 if cuda:
                     ring = torch.zeros((2, 1 + 2 * B), dtype=torch.int32).pin_memory()
                     events = [torch.cuda.Event(), torch.cuda.Event()]
@@ -916,7 +1012,7 @@ class ChatGLMDecoder:
                 while steps < max_steps:
                     n = min(poll, max_steps - steps)
                     for _ in range(n):
-                        sess.decode_step(greedy=False, rows=True)
+                        sess.decode_step(greedy=False, rows=True, pen=pen)
                     steps += n
                     if not cuda:
                         if int(sess.rows.live[0]) == 0:
@@ -945,7 +1041,7 @@ class ChatGLMDecoder:
             "invalid": [b for b in range(B) if int(state[b, 1]) & fused_ops.BatchRows.INVALID],
             "prefill_s": t_first, "sum_s": total,
             "gen_tok_per_s": (gen - sum(1 for c in counts if c)) / rest if steps and rest > 0 else float("nan"),
-            "avg_tok_per_s": gen / total if total > 0 else float("nan"),
+            "avg_tok_per_s": gen / total if total > 0 else float("nan"), "penalties": bool(pen),
         }
         if self.time_log:
             s = self.last_stats

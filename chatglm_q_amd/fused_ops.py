@@ -543,3 +543,178 @@ def batch_sample_advance(logits: Tensor, tok: Tensor, rows: BatchRows, write_ind
     if return_distribution:
         return probs, idx, u
     return None
+
+
+# ---- sampling controls: repetition / presence / frequency penalties and a logit bias (csrc/logit_penalties.hip) -----------------------
+LOGIT_BIAS_MAX = 64          # entries of one row's logit-bias list (QL_LOGIT_BIAS_MAX, include/qlinear_hip.h); more raise a ValueError
+_PROMPT_BIT = -(2 ** 31)     # bit 31 of a state word as an int32
+
+
+def _finite(v) -> bool:
+    return v == v and v not in (float("inf"), float("-inf"))
+
+
+class PenaltyState:
+    """Static buffers of ``logit_penalties`` for a batch of rows (a captured step reads and updates them in place): ``counts``
+    (batch, ld) int32 - bit 31: the entry is one of the row's prompt ids, bits 0..30: how often the row has generated it;
+    ``settings`` (batch, 3) float32 = repetition, presence, frequency penalty; ``bias_ids`` / ``bias_vals`` (batch, LOGIT_BIAS_MAX)
+    int32 / float32 and ``bias_len`` (batch,) int32: every row's sparse logit bias.  ``active``: whether the last ``arm`` set anything
+    that changes a logit (all defaults: nothing has to be launched)."""
+
+    def __init__(self, batch: int, vocab: int, device):
+        if batch < 1 or vocab < 1:
+            raise ValueError(f"PenaltyState: batch >= 1 and vocab >= 1 (got {batch}, {vocab})")
+        self.batch, self.vocab, self.device = batch, vocab, torch.device(device)
+        self.ld = -(-vocab // 4) * 4                            # rows of the state stay 16-byte aligned
+        self.counts = torch.zeros((batch, self.ld), dtype=torch.int32, device=device)
+        self.settings = torch.tensor([[1.0, 0.0, 0.0]] * batch, dtype=torch.float32, device=device)
+        self.bias_ids = torch.zeros((batch, LOGIT_BIAS_MAX), dtype=torch.int32, device=device)
+        self.bias_vals = torch.zeros((batch, LOGIT_BIAS_MAX), dtype=torch.float32, device=device)
+        self.bias_len = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.active = False
+
+    @staticmethod
+    def check(batch: int, vocab: int, settings, biases):
+        """Validate one (repetition, presence, frequency) triple and one bias dict (or None) per row; returns them normalised:
+        a list of float triples and a list of [(id, value), ...] lists.  A ValueError names the offending row."""
+        if len(settings) != batch or len(biases) != batch:
+            raise ValueError(f"penalties: {len(settings)} settings and {len(biases)} bias lists for {batch} rows")
+        out_s, out_b = [], []
+        for b, (s, bias) in enumerate(zip(settings, biases)):
+            r, p, f = (float(v) for v in s)
+            if not (_finite(r) and r > 0):
+                raise ValueError(f"penalties: row {b}: repetition_penalty must be finite and > 0 (got {r})")
+            if not _finite(p):
+                raise ValueError(f"penalties: row {b}: presence_penalty must be finite (got {p})")
+            if not _finite(f):
+                raise ValueError(f"penalties: row {b}: frequency_penalty must be finite (got {f})")
+            pairs = []
+            if bias:
+                items = list(bias.items()) if hasattr(bias, "items") else [tuple(e) for e in bias]
+                if len(items) > LOGIT_BIAS_MAX:
+                    raise ValueError(f"penalties: row {b}: {len(items)} logit_bias entries, at most {LOGIT_BIAS_MAX} (LOGIT_BIAS_MAX)")
+                seen = set()
+                for i, v in items:
+                    if int(i) != i or not 0 <= int(i) < vocab:
+                        raise ValueError(f"penalties: row {b}: logit_bias id {i} outside the vocabulary [0, {vocab})")
+                    if int(i) in seen:
+                        raise ValueError(f"penalties: row {b}: logit_bias id {int(i)} given twice")
+                    seen.add(int(i))
+                    v = float(v)
+                    if v != v or v == float("inf"):
+                        raise ValueError(f"penalties: row {b}: logit_bias value for id {int(i)} must be finite or -inf (got {v})")
+                    pairs.append((int(i), v))
+            out_s.append((r, p, f))
+            out_b.append(pairs)
+        return out_s, out_b
+
+    @staticmethod
+    def neutral(settings, biases) -> bool:
+        """True when the (validated) settings change no logit: every row at (1, 0, 0) with an empty bias list."""
+        return all(s == (1.0, 0.0, 0.0) for s in settings) and not any(biases)
+
+    def arm(self, prompts_or_mask, settings, biases=None):
+        """Start a generation, in place (the buffers keep their addresses): the counts go to 0, the prompt flags are set from
+        ``prompts_or_mask`` - one sequence of REAL prompt ids per row (no pads), or a bool (batch, vocab) membership tensor - and
+        the settings (one (repetition, presence, frequency) per row) and bias dicts ``{id: value}`` (one per row or None) are
+        validated and stored."""
+        B, N = self.batch, self.vocab
+        settings, biases = self.check(B, N, settings, [None] * B if biases is None else biases)
+        self.counts.zero_()
+        if isinstance(prompts_or_mask, Tensor):
+            if prompts_or_mask.dtype != torch.bool or tuple(prompts_or_mask.shape) != (B, N):
+                raise ValueError(f"PenaltyState.arm: a prompt mask must be a bool ({B}, {N}) tensor")
+            self.counts[:, :N].masked_fill_(prompts_or_mask.to(self.device), _PROMPT_BIT)
+        else:
+            if len(prompts_or_mask) != B:
+                raise ValueError(f"PenaltyState.arm: {len(prompts_or_mask)} prompts for {B} rows")
+            flat = []
+            for b, ids in enumerate(prompts_or_mask):
+                for i in ids:
+                    if not 0 <= int(i) < N:
+                        raise ValueError(f"PenaltyState.arm: row {b}: prompt id {int(i)} outside the vocabulary [0, {N})")
+                    flat.append(b * self.ld + int(i))
+            if flat:
+                self.counts.view(-1).index_fill_(0, torch.tensor(flat, dtype=torch.long).to(self.device), _PROMPT_BIT)
+        ids = torch.zeros((B, LOGIT_BIAS_MAX), dtype=torch.int32)
+        vals = torch.zeros((B, LOGIT_BIAS_MAX), dtype=torch.float32)
+        for b, pairs in enumerate(biases):
+            for j, (i, v) in enumerate(pairs):
+                ids[b, j], vals[b, j] = i, v
+        self.settings.copy_(torch.tensor(settings, dtype=torch.float32))
+        self.bias_ids.copy_(ids)
+        self.bias_vals.copy_(vals)
+        self.bias_len.copy_(torch.tensor([len(p) for p in biases], dtype=torch.int32))
+        self.active = not self.neutral(settings, biases)
+        return self
+
+    def generated(self) -> Tensor:
+        """(batch, vocab) int32: how often every row has generated every id so far."""
+        return self.counts[:, :self.vocab] & 0x7FFFFFFF
+
+    def tensors(self):
+        """What a step changes (a capture saves and restores it)."""
+        return (self.counts,)
+
+
+def _logit_penalties_host(logits: Tensor, state: PenaltyState, tok, row_state):
+    """CPU form of qlinear_logit_penalties: the same rules with torch ops, every op one fp32 rounding (torch does not fuse them)."""
+    B, N = logits.shape
+    live = torch.ones(B, dtype=torch.bool) if row_state is None else (row_state[:, 1] & BatchRows.FINISHED) == 0
+    words = state.counts[:, :N]
+    if tok is not None:
+        for b in range(B):
+            t = int(tok[b])
+            if bool(live[b]) and 0 <= t < N:
+                words[b, t] += 1
+    g = words & 0x7FFFFFFF
+    seen, counted = words != 0, g > 0
+    r, p, f = (state.settings[:, k:k + 1] for k in range(3))
+    x = logits.float()
+    x = torch.where(seen, torch.where(x > 0, x / r, x * r), x)
+    m = f * g.float()
+    x = torch.where(counted, (x - m) - p, x)
+    biased = torch.zeros((B, N), dtype=torch.bool)
+    bias = torch.zeros((B, N), dtype=torch.float32)
+    for b in range(B):
+        n = int(state.bias_len[b])
+        if n:
+            ids = state.bias_ids[b, :n].long()
+            biased[b, ids] = True
+            bias[b, ids] = state.bias_vals[b, :n]
+    x = torch.where(biased, x + bias, x)
+    touched = (seen | biased) & live[:, None]
+    logits.copy_(torch.where(touched, x.to(logits.dtype), logits))
+
+
+def logit_penalties(logits: Tensor, state: PenaltyState, tok: Tensor | None = None, row_state: Tensor | None = None) -> Tensor:
+    """Apply ``state``'s repetition / presence / frequency penalties and logit bias to `logits` (B, N) IN PLACE and advance the
+    token history, in one launch (``qlinear_logit_penalties``, whose comment in include/qlinear_hip.h holds the rules).  ``tok`` (B,)
+    int64: the ids fed into this step - counted before the rules are applied; None (the first token after a prefill): nothing is
+    counted.  ``row_state``: a ``BatchRows.row_state``; rows whose FINISHED bit is set are left untouched.  Returns `logits`.  CPU
+    tensors take the host form (torch ops, the same rules bit for bit)."""
+    if logits.dim() != 2 or logits.shape[1] < 1 or logits.stride(1) != 1:
+        raise ValueError(f"logit_penalties: logits must be (B, N) with N >= 1 and unit column stride, got {tuple(logits.shape)}")
+    B, N = logits.shape
+    if B != state.batch or N != state.vocab:
+        raise ValueError(f"logit_penalties: logits {tuple(logits.shape)} for a PenaltyState of ({state.batch}, {state.vocab})")
+    if B > 1 and logits.stride(0) < N:
+        raise ValueError("logit_penalties: overlapping logits rows")
+    if tok is not None and (tok.dtype != torch.int64 or tok.numel() != B or not tok.is_contiguous()):
+        raise ValueError("logit_penalties: tok must be a contiguous int64 tensor of B elements")
+    if row_state is not None and (row_state.dtype != torch.int32 or tuple(row_state.shape) != (B, 2) or not row_state.is_contiguous()):
+        raise ValueError("logit_penalties: row_state must be a contiguous int32 (B, 2) tensor (BatchRows.row_state)")
+    for t in (state.counts, tok, row_state):
+        if t is not None and t.device != logits.device:
+            raise ValueError(f"logit_penalties: logits on {logits.device}, state on {t.device}")
+    if not logits.is_cuda:
+        _logit_penalties_host(logits, state, None if tok is None else tok.view(-1), row_state)
+        return logits
+    lib = _lib.get_lib()
+    with torch.cuda.device(logits.device):
+        st = lib.qlinear_logit_penalties(logits.data_ptr(), B, N, logits.stride(0) if B > 1 else N, state.settings.data_ptr(),
+                                         state.bias_ids.data_ptr(), state.bias_vals.data_ptr(), state.bias_len.data_ptr(),
+                                         LOGIT_BIAS_MAX, state.counts.data_ptr(), state.ld, _lib.ptr(tok), _lib.ptr(row_state),
+                                         _lib.dtype_code(logits.dtype), _lib.stream_ptr(logits.device))
+    _lib.check(st, "qlinear_logit_penalties")
+    return logits

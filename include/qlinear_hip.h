@@ -47,7 +47,9 @@ extern "C" {
 /* 3 (round 6): qlinear_top_p_sample added; round 5's additions (qlinear_w4g32_unpack_gemv, qlinear_dispatch_flags,
  * qlinear_w4g32_packed_dispatch, QL_K code 19 = ROWS16, qlinear_gated_serves weight_bits 88 = int8 x int8) had gone out under 2.
  * Still 3: qlinear_token_logprob added - purely additive, no existing entry point changed its signature or its meaning.
- * Still 3: qlinear_batch_sample_advance added - purely additive as well. */
+ * Still 3: qlinear_batch_sample_advance added - purely additive as well.
+ * Still 3: qlinear_logit_penalties (and the constant QL_LOGIT_BIAS_MAX) added - purely additive; the selection entry points
+ * (qlinear_greedy_advance, qlinear_top_p_sample, qlinear_batch_sample_advance) are unchanged, they read the adjusted logits. */
 #define QLINEAR_ABI_VERSION 3
 
 /* activation dtypes */
@@ -528,6 +530,36 @@ int qlinear_batch_sample_advance(const void* logits, int64_t B, int64_t N, int64
                                  int32_t* row_state, const int32_t* budget, int64_t* out_tokens, int64_t out_ld, int32_t* live,
                                  int64_t stop_id, int64_t* tok, int64_t* write_index, int64_t* pos, float* mask, int64_t capacity,
                                  float* probs_out, int64_t* index_out, float* u_out, int64_t dist_ld, int dtype, void* stream);
+/* Sampling controls in one launch between lm_head and the selection entry points above: a repetition penalty, OpenAI-style presence
+ * and frequency penalties and a sparse logit bias, applied IN PLACE to logits (B, N) (row stride ldl, unit column stride), with the
+ * token history they need kept in device memory - the launch can sit inside a captured decode step.
+ *   state (B, lds) int32, lds >= N: word [b][v] = bit 31: v is one of row b's prompt ids (P); bits 0..30: how often row b has generated
+ *     v (G).  The caller zeroes it and sets the prompt bits when a generation starts; this entry point advances the counts.
+ *   settings (B, 3) float: r (repetition penalty, > 0; 1 = off), p (presence penalty; 0 = off), f (frequency penalty; 0 = off).
+ *   bias_ids / bias_vals (B, bias_cap) int32 / float, bias_len (B) int32: row b's bias list is its first bias_len[b] pairs (clamped to
+ *     [0, bias_cap]); ids distinct and in [0, N) (others are ignored), values finite or -inf.  bias_cap <= QL_LOGIT_BIAS_MAX;
+ *     bias_cap == 0: no lists, the three pointers may be null.  All of these are read from device memory at run time, so ONE
+ *     captured graph serves every setting.
+ *   tok (B) int64, nullable: the id fed into this step.  First, state[b][tok[b]] += 1 (an id outside [0, N) counts nothing; null - the
+ *     first token after a prefill - counts nothing), so G always covers exactly the tokens generated so far.
+ *   row_state (B, 2) int32, nullable: qlinear_batch_sample_advance's; a row whose finished bit (bit 0 of [b][1]) is set is left
+ *     entirely untouched - no count, no write.
+ * Then for every entry, x = float(logits[b][v]), each line ONE fp32 operation rounded to nearest (no fused multiply-add):
+ *     P || G > 0 :  x = x > 0 ? x / r : x * r        (the Hugging Face rule; a NaN takes the multiply and stays NaN)
+ *     G > 0      :  m = f * float(G);  x = x - m;  x = x - p
+ *     biased     :  x = x + bias
+ * and the result is rounded once to the logits dtype (nearest even) and stored.  An entry no rule touches keeps its bits.  -inf,
+ * +inf and NaN logits pass through as IEEE arithmetic dictates.
+ * Every entry is owned by exactly one thread (no atomics; plain vector loads and stores).  Any N >= 1; logits aligned to its element size
+ * only: rows (of logits and of state) that are 16-byte aligned go through 16-byte accesses, the ragged end of a row and rows that
+ * are not aligned go entry by entry.  Nothing outside [row, row + N) is touched.  One pass over B x N x (element + 4) bytes.
+ * QL_ERR_BAD_DTYPE; QL_ERR_BAD_SHAPE for N < 1, ldl < N, lds < N, B > 65535 or bias_cap outside [0, QL_LOGIT_BIAS_MAX];
+ * QL_ERR_NULL_POINTER for a missing logits / settings / state (or a missing bias array with bias_cap > 0); B == 0 is QL_OK without a
+ * launch. */
+#define QL_LOGIT_BIAS_MAX 64
+int qlinear_logit_penalties(void* logits, int64_t B, int64_t N, int64_t ldl, const float* settings, const int32_t* bias_ids,
+                            const float* bias_vals, const int32_t* bias_len, int64_t bias_cap, int32_t* state, int64_t lds,
+                            const int64_t* tok, const int32_t* row_state, int dtype, void* stream);
 
 #ifdef __cplusplus
 }
