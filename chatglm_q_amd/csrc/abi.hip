@@ -812,4 +812,21 @@ int qlinear_logit_penalties(void* logits, int64_t B, int64_t N, int64_t ldl, con
                            (hipStream_t)stream);
 }
 
+int qlinear_gptq_block(const float* W, int64_t n_rows, int64_t ldw, int64_t c0, int64_t bc, const float* hinv_block, int64_t ldh, int bits,
+                       int64_t group, float* Q, float* Err, float* Loss, float* scale, int64_t lds, int dtype, void* stream) {
+    if (dtype != QL_DTYPE_F32) return QL_ERR_BAD_DTYPE;
+    if (bits != 4 && bits != 8) return QL_ERR_UNSUPPORTED;
+    if (n_rows < 0 || n_rows >= ((int64_t)1 << 31) || bc < 1 || bc > 128 || c0 < 0 || c0 >= ((int64_t)1 << 31) || ldw < c0 + bc || ldh < bc)
+        return QL_ERR_BAD_SHAPE;
+    if (bits == 4) {
+        if (group != 32) return QL_ERR_UNSUPPORTED;
+        if (bc % group != 0 || c0 % group != 0 || lds < n_rows) return QL_ERR_BAD_SHAPE;
+    }
+    if (n_rows == 0) return QL_OK;
+    if (!W || !hinv_block || !Q || !Err || !Loss || !scale) return QL_ERR_NULL_POINTER;
+    if (!aligned(W, 4) || !aligned(hinv_block, 4) || !aligned(Q, 4) || !aligned(Err, 4) || !aligned(Loss, 4) || !aligned(scale, 4))
+        return QL_ERR_MISALIGNED;
+    return gptq_block(bits, W, n_rows, ldw, c0, bc, hinv_block, ldh, Q, Err, Loss, scale, lds, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -298,6 +298,10 @@ int logit_penalties(int dtype, void* logits, int64_t B, int64_t N, int64_t ldl, 
                     const float* bias_vals, const int32_t* bias_len, int64_t bias_cap, int32_t* state, int64_t lds, const int64_t* tok,
                     const int32_t* row_state, hipStream_t st);
 
+// gptq.hip: the column walk of one GPTQ block (at most 128 columns) over all weight rows in one launch; fp32
+int gptq_block(int bits, const float* W, int64_t n_rows, int64_t ldw, int64_t c0, int64_t bc, const float* H, int64_t ldh, float* Q,
+               float* Err, float* Loss, float* scale, int64_t lds, hipStream_t st);
+
 // prefill_attention.hip: many-position attention in one launch (D = 128, H = 16 G, fp16 / bf16)
 int prefill_attention(int dtype, const void* Q, const void* Kc, const void* Vc, const float* mask, const uint8_t* flags, void* Out,
                       int64_t B, int64_t S, int64_t Tkv, int64_t H, int64_t G, int64_t cap, int64_t ldm, hipStream_t st);

@@ -718,3 +718,75 @@ def logit_penalties(logits: Tensor, state: PenaltyState, tok: Tensor | None = No
                                          _lib.dtype_code(logits.dtype), _lib.stream_ptr(logits.device))
     _lib.check(st, "qlinear_logit_penalties")
     return logits
+
+
+# ---- GPTQ: the column walk of one block (csrc/gptq.hip) ------------------------------------------------------------------------------
+GPTQ_MAX_BLOCK = 128
+
+
+def _gptq_block_host(weight: Tensor, c0: int, bc: int, hinv: Tensor, bits: int, scale: Tensor, group: int):
+    """The column walk with torch ops, all rows at once and one column per iteration: the reference's inner loop
+    (chatglm_q/int4/quantizer.py:151-167, chatglm_q/int8/quantizer.py:126-137).  Every op is one fp32 rounding."""
+    qmax = 7 if bits == 4 else 127
+    w = weight[:, c0:c0 + bc].clone()
+    h = hinv[c0:c0 + bc, c0:c0 + bc]
+    Q, Err, Loss = torch.empty_like(w), torch.empty_like(w), torch.empty_like(w)
+    s = scale if bits == 8 else None
+    for j in range(bc):
+        if bits == 4 and j % group == 0:
+            s = torch.clamp(w[:, j:j + group].abs().amax(dim=1) / qmax, min=1e-10)
+            scale[(c0 + j) // group] = s
+        d = h[j, j]
+        col = w[:, j]
+        q = s * torch.clamp(torch.round(col / s), -qmax, qmax)
+        e = col - q
+        err = e / d
+        Q[:, j], Err[:, j], Loss[:, j] = q, err, ((e * e) / (d * d)) * 0.5
+        if j + 1 < bc:
+            w[:, j + 1:] -= err[:, None] * h[j, j + 1:][None, :]
+    return Q, Err, Loss
+
+
+def gptq_block(weight: Tensor, c0: int, bc: int, hinv: Tensor, bits: int, scale: Tensor, group: int = 32, use_kernel: bool | None = None):
+    """GPTQ over the input columns [c0, c0 + bc) of ``weight`` (n_rows, n_columns; nn.Linear layout, fp32), bc <= 128, with the
+    upper Cholesky factor ``hinv`` (n_columns, n_columns) of the inverse Hessian: returns ``(Q, Err, Loss)``, each (n_rows, bc) -
+    the grid values, the scaled errors and the loss terms (the rules: qlinear_gptq_block in include/qlinear_hip.h).  ``bits`` 4:
+    ``scale`` (n_columns / group, n_rows) gets its rows c0 / group ... WRITTEN; ``bits`` 8: ``scale`` (n_rows) is read.  ``weight``
+    is not modified: the caller subtracts ``Err @ hinv[c0:c0+bc, c0+bc:]`` from the columns to the right before the next block.
+    GPU tensors take ONE launch of the HIP kernel, anything else the same formula in torch ops (``use_kernel`` forces either)."""
+    if bits not in (4, 8):
+        raise ValueError(f"gptq_block: bits must be 4 or 8, got {bits}")
+    if weight.dim() != 2 or hinv.dim() != 2 or hinv.shape[0] != hinv.shape[1] or hinv.shape[0] != weight.shape[1]:
+        raise ValueError(f"gptq_block: weight {tuple(weight.shape)} does not go with a factor of {tuple(hinv.shape)}")
+    n_rows, n_cols = weight.shape
+    if not (1 <= bc <= GPTQ_MAX_BLOCK and 0 <= c0 and c0 + bc <= n_cols):
+        raise ValueError(f"gptq_block: columns [{c0}, {c0 + bc}) of {n_cols} (at most {GPTQ_MAX_BLOCK} per block)")
+    if bits == 4:
+        if group < 2 or group % 2 or bc % group or c0 % group or n_cols % group:
+            raise ValueError(f"gptq_block: group {group} does not divide columns [{c0}, {c0 + bc}) of {n_cols}")
+        want = (n_cols // group, n_rows)
+    else:
+        want = (n_rows,)
+    if tuple(scale.shape) != want or scale.dtype != torch.float32 or not scale.is_contiguous():
+        raise ValueError(f"gptq_block: scale must be a contiguous float32 tensor of shape {want}")
+    for t in (weight, hinv):
+        if t.dtype != torch.float32 or t.stride(1) != 1:
+            raise ValueError("gptq_block: weight and hinv must be float32 with unit column stride")
+    if hinv.device != weight.device or scale.device != weight.device:
+        raise ValueError("gptq_block: weight, hinv and scale must be on one device")
+    if use_kernel is None:
+        use_kernel = weight.is_cuda
+    if not use_kernel:
+        return _gptq_block_host(weight, c0, bc, hinv, bits, scale, group)
+    if not weight.is_cuda:
+        raise ValueError("gptq_block: the kernel needs GPU tensors")
+    lib = _lib.get_lib()
+    Q, Err, Loss = (torch.empty((n_rows, bc), dtype=torch.float32, device=weight.device) for _ in range(3))
+    ldw = weight.stride(0) if n_rows > 1 else n_cols
+    ldh = hinv.stride(0) if n_cols > 1 else 1
+    with torch.cuda.device(weight.device):
+        st = lib.qlinear_gptq_block(weight.data_ptr(), n_rows, ldw, c0, bc, hinv.data_ptr() + 4 * (c0 * ldh + c0), ldh, bits, group,
+                                    Q.data_ptr(), Err.data_ptr(), Loss.data_ptr(), scale.data_ptr(), n_rows,
+                                    _lib.dtype_code(weight.dtype), _lib.stream_ptr(weight.device))
+    _lib.check(st, "qlinear_gptq_block")
+    return Q, Err, Loss

@@ -49,7 +49,8 @@ extern "C" {
  * Still 3: qlinear_token_logprob added - purely additive, no existing entry point changed its signature or its meaning.
  * Still 3: qlinear_batch_sample_advance added - purely additive as well.
  * Still 3: qlinear_logit_penalties (and the constant QL_LOGIT_BIAS_MAX) added - purely additive; the selection entry points
- * (qlinear_greedy_advance, qlinear_top_p_sample, qlinear_batch_sample_advance) are unchanged, they read the adjusted logits. */
+ * (qlinear_greedy_advance, qlinear_top_p_sample, qlinear_batch_sample_advance) are unchanged, they read the adjusted logits.
+ * Still 3: qlinear_gptq_block added - purely additive. */
 #define QLINEAR_ABI_VERSION 3
 
 /* activation dtypes */
@@ -560,6 +561,31 @@ int qlinear_batch_sample_advance(const void* logits, int64_t B, int64_t N, int64
 int qlinear_logit_penalties(void* logits, int64_t B, int64_t N, int64_t ldl, const float* settings, const int32_t* bias_ids,
                             const float* bias_vals, const int32_t* bias_len, int64_t bias_cap, int32_t* state, int64_t lds,
                             const int64_t* tok, const int32_t* row_state, int dtype, void* stream);
+
+/* GPTQ (chatglm_q/int4/quantizer.py:151-167, chatglm_q/int8/quantizer.py:126-137): the column walk of ONE block of bc <= 128 input
+ * columns over all weight rows in one launch.  All arrays fp32 device memory (dtype must be QL_DTYPE_F32).
+ *   W (n_rows, row stride ldw): the working weights, nn.Linear layout; columns [c0, c0 + bc) are read, nothing is written back.
+ *   hinv_block: address of Hinv[c0][c0] of the upper Cholesky factor of the inverse Hessian, row stride ldh; rows / columns
+ *     [0, bc) of the block are read (the upper triangle and the diagonal).
+ *   bits 4: group must be 32 (QL_ERR_UNSUPPORTED otherwise), bc and c0 multiples of it; scale is the (n_columns / group, lds)
+ *     array, lds >= n_rows: rows c0 / group .. (c0 + bc) / group - 1, entries [0, n_rows), are WRITTEN.
+ *   bits 8: any 1 <= bc <= 128; scale (n_rows) is READ; group and lds are ignored.
+ *   Q, Err, Loss (n_rows, bc) contiguous: written.
+ * Per row r, for j = 0 .. bc-1, every line ONE fp32 operation rounded to nearest (no fused multiply-add), w[] the row's current
+ * block values, d = hinv_block[j][j], qmax = 7 / 127:
+ *     bits 4, j % group == 0:  m = max_{t<group} |w[j+t]|;  s = max(m / 7.0f, 1e-10f);  scale[(c0+j)/group][r] = s
+ *     bits 8:                  s = scale[r]
+ *     x = w[j] / s;  c = min(max(rintf(x), -qmax), qmax);  q = s * c                    Q[r][j] = q
+ *     e = w[j] - q;  Loss[r][j] = ((e * e) / (d * d)) * 0.5f;  err = e / d              Err[r][j] = err
+ *     for t in j+1 .. bc-1:  p = err * hinv_block[j][t];  w[t] = w[t] - p
+ * Rows are independent: one lane per row, every output element has one owner, plain vector loads and stores, no atomics.  Nothing
+ * outside the stated ranges is touched.  The caller applies Err to the columns right of the block (W[:, c0+bc:] -= Err . Hinv[c0:c0+bc,
+ * c0+bc:]) before the next block.
+ * QL_ERR_BAD_DTYPE; QL_ERR_UNSUPPORTED for bits other than 4 / 8 or an int4 group other than 32; QL_ERR_BAD_SHAPE for bc outside
+ * [1, 128], ldw < c0 + bc, ldh < bc, (int4) bc or c0 no multiple of the group or lds < n_rows; QL_ERR_NULL_POINTER; n_rows == 0 is QL_OK
+ * without a launch. */
+int qlinear_gptq_block(const float* W, int64_t n_rows, int64_t ldw, int64_t c0, int64_t bc, const float* hinv_block, int64_t ldh, int bits,
+                       int64_t group, float* Q, float* Err, float* Loss, float* scale, int64_t lds, int dtype, void* stream);
 
 #ifdef __cplusplus
 }
