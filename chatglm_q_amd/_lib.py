@@ -138,6 +138,8 @@ EXPORTS = {
                                         c_void_p, c_void_p, c_int, c_void_p]),
     "qlinear_gptq_block": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_int64, c_int, c_void_p]),
+    "qlinear_step_logprobs": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_int64, c_int64, c_int, c_void_p]),
     "qlinear_masked_softmax": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
                                        c_int, c_void_p]),
     "qlinear_silu_mul": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]),

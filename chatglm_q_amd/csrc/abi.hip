@@ -812,6 +812,18 @@ int qlinear_logit_penalties(void* logits, int64_t B, int64_t N, int64_t ldl, con
                            (hipStream_t)stream);
 }
 
+int qlinear_step_logprobs(const void* logits, int64_t B, int64_t N, int64_t ldl, const int64_t* tok, const int32_t* row_state,
+                          int32_t* count, float* chosen, int32_t* top_ids, float* top_lp, int64_t cap, int64_t n_top, int dtype,
+                          void* stream) {
+    if (!dtype_ok(dtype)) return QL_ERR_BAD_DTYPE;
+    if (B < 0 || B > 65535 || !fits_i32(N) || ldl < N || cap < 1 || n_top < 0 || n_top > QL_TOP_LOGPROBS_MAX) return QL_ERR_BAD_SHAPE;
+    if (B == 0) return QL_OK;
+    if (!logits || !tok || !count || !chosen) return QL_ERR_NULL_POINTER;
+    if (n_top > 0 && !(top_ids && top_lp)) return QL_ERR_NULL_POINTER;
+    if (!aligned(logits, (size_t)esize(dtype))) return QL_ERR_MISALIGNED;
+    return step_logprobs(dtype, logits, B, N, ldl, tok, row_state, count, chosen, top_ids, top_lp, cap, n_top, (hipStream_t)stream);
+}
+
 int qlinear_gptq_block(const float* W, int64_t n_rows, int64_t ldw, int64_t c0, int64_t bc, const float* hinv_block, int64_t ldh, int bits,
                        int64_t group, float* Q, float* Err, float* Loss, float* scale, int64_t lds, int dtype, void* stream) {
     if (dtype != QL_DTYPE_F32) return QL_ERR_BAD_DTYPE;

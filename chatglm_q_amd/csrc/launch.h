@@ -293,6 +293,10 @@ int batch_sample_advance(int dtype, const void* logits, int64_t B, int64_t N, in
 int token_logprob(int dtype, const void* logits, int64_t R, int64_t N, int64_t ldl, const int64_t* targets, int64_t ignore_index,
                   float* logprob_out, float* lse_out, int64_t* argmax_out, hipStream_t st);
 
+// logprob.hip: one generation step's record - the chosen token's log-prob and the n_top most likely alternatives, kept on the device
+int step_logprobs(int dtype, const void* logits, int64_t B, int64_t N, int64_t ldl, const int64_t* tok, const int32_t* row_state,
+                  int32_t* count, float* chosen, int32_t* top_ids, float* top_lp, int64_t cap, int64_t n_top, hipStream_t st);
+
 // logit_penalties.hip: repetition / presence / frequency penalties + sparse logit bias in place, token history kept on the device
 int logit_penalties(int dtype, void* logits, int64_t B, int64_t N, int64_t ldl, const float* settings, const int32_t* bias_ids,
                     const float* bias_vals, const int32_t* bias_len, int64_t bias_cap, int32_t* state, int64_t lds, const int64_t* tok,

@@ -65,6 +65,33 @@ class ScoreResult:
         self.logprobs, self.valid, self.loss, self.argmax, self.logits = logprobs, valid, loss, argmax, logits
 
 
+class GenerationLogprobs:
+    """What a generation with ``logprobs=n`` leaves in ``ChatGLMDecoder.last_logprobs`` for one sequence, one entry per token
+    returned: ``token_logprobs[t]`` = log p(token t | everything before it) under the logits the selection read (after penalties
+    and bias, before temperature / top-k / top-p); ``top_ids[t]`` / ``top_logprobs[t]`` = the n most likely ids at that step (most
+    likely first, ties: lowest id first) and their log-probs."""
+    __slots__ = ("token_logprobs", "top_ids", "top_logprobs")
+
+    def __init__(self, token_logprobs, top_ids, top_logprobs):
+        self.token_logprobs, self.top_ids, self.top_logprobs = token_logprobs, top_ids, top_logprobs
+
+    def __len__(self):
+        return len(self.token_logprobs)
+
+    def __repr__(self):
+        return f"GenerationLogprobs({len(self)} tokens, {len(self.top_ids[0]) if self.top_ids else 0} alternatives)"
+
+
+def check_logprobs(logprobs) -> Optional[int]:
+    """``logprobs`` of generate_ids / generate_batch_ids: None = off, an int in [0, TOP_LOGPROBS_MAX] = that many alternatives."""
+    from .fused_ops import TOP_LOGPROBS_MAX
+    if logprobs is None:
+        return None
+    if isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= TOP_LOGPROBS_MAX:
+        raise ValueError(f"logprobs must be None or an int in [0, {TOP_LOGPROBS_MAX}] (got {logprobs!r})")
+    return int(logprobs)
+
+
 class DecodeSession:
     """One sequence batch on one device: preallocated cache, eager (chunked) prefill, graph-replayed decode."""
 
@@ -113,6 +140,9 @@ class DecodeSession:
         # sampling controls (arm_penalties): token history, penalties and logit bias in device memory, read and updated by the
         # "+pen" steps.  Allocated by the first penalised generation: a session that never uses them holds nothing extra
         self.pen = None
+        # the record of the "+lp" steps (arm_logprobs): every generated token's log-prob and the most likely alternatives, appended
+        # on the device and read once at the end.  Allocated by the first generation that asks for log-probs
+        self.lp = None
         self.length = 0
         self.busy = False                                       # a generate_ids generator is running on this session
 
@@ -316,6 +346,24 @@ class DecodeSession:
         lg = logits if logits.stride(-1) == 1 else logits.contiguous()
         return fused_ops.logit_penalties(lg, self.pen, None, self.rows.row_state if rows else None)
 
+    def arm_logprobs(self, on: bool = True) -> bool:
+        """Arm the log-prob record for a new generation (``fused_ops.StepLogprobs``: allocated on first use, one entry per cache
+        position, TOP_LOGPROBS_MAX alternatives wide) - nothing recorded yet.  ``on`` False: nothing is armed or allocated and the
+        generation takes the steps without the record's launch.  Returns ``on``."""
+        if not on:
+            return False
+        if self.lp is None:
+            from . import fused_ops
+            self.lp = fused_ops.StepLogprobs(self.batch, self.capacity, self.device)
+        self.lp.arm()
+        return True
+
+    def logprobs_first(self, logits: Tensor, rows: bool = False) -> None:
+        """Record the first token after a prefill: the eager launch behind ``sample_first`` / ``sample_rows_first`` / the host's
+        choice, once ``tok`` holds the id, on the prefill's last-position logits (after ``penalize_first``)."""
+        from . import fused_ops
+        fused_ops.step_logprobs(logits, self.tok.view(-1), self.lp, self.rows.row_state if rows else None)
+
     def sample_first(self, logits: Tensor) -> Tensor:
         """The token after a prefill, drawn by the device sampler from the prefill's last-position logits (no bookkeeping: prefill
         armed the step state).  Returns the (batch,) device tensor; ``tok`` holds it as the next step's input."""
@@ -329,10 +377,10 @@ class DecodeSession:
         budget per row, and the stop id (None: none).  The captured "rows" step bakes the stop id in: a different one drops it."""
         self.rows.arm(params, seeds, budgets, stop_id)
         if self._rows_stop is not None and self._rows_stop != self.rows.stop_id:
-            for mode in ("rows", "rows+pen"):
+            for mode in [m for m in self._graphs if m.startswith("rows")]:       # "rows", "rows+pen", "rows+lp", "rows+pen+lp"
                 self._graphs.pop(mode, None)
                 self._graph_logits.pop(mode, None)
-            if self._captured_mode in ("rows", "rows+pen"):
+            if self._captured_mode is not None and self._captured_mode.startswith("rows"):
                 self.graph = self._captured_mode = None
             self._rows_stop = None
 
@@ -342,7 +390,7 @@ class DecodeSession:
         from . import fused_ops
         fused_ops.batch_sample_advance(logits, self.tok.view(-1), self.rows)
 
-    def _step_body(self, greedy: bool, sample: bool = False, rows: bool = False, pen: bool = False):
+    def _step_body(self, greedy: bool, sample: bool = False, rows: bool = False, pen: bool = False, lp: bool = False):
         # invariant on entry: mask is 0 for positions <= write_index (the new position may attend to itself)
         logits = self.model.step(self.tok, self.cache, self.write_index, self.pos, self.mask, last_only=True)
         if pen and (greedy or sample or rows):                  # count the id this step was fed, adjust the logits in place: one launch
@@ -352,6 +400,8 @@ class DecodeSession:
             from . import fused_ops                             # the tokens live in rows.out_tokens (self.logits is not touched)
             fused_ops.batch_sample_advance(logits[:, -1], self.tok.view(-1), self.rows, self.write_index, self.pos.view(-1),
                                            self.mask)
+            if lp:                                              # the record's launch, directly behind the selection (all three modes)
+                fused_ops.step_logprobs(logits[:, -1], self.tok.view(-1), self.lp, self.rows.row_state)
             return
         self.logits = logits[:, -1]
         if sample:                                              # the reference's sampler + the bookkeeping: one launch
@@ -359,13 +409,20 @@ class DecodeSession:
             lg = self.logits if self.logits.stride(-1) == 1 else self.logits.contiguous()
             fused_ops.top_p_sample(lg, self.tok.view(-1), self.rng_state, dev_params=self.sample_params,
                                    write_index=self.write_index, pos=self.pos.view(-1), mask=self.mask)
+            if lp:
+                fused_ops.step_logprobs(lg, self.tok.view(-1), self.lp)
             return
         if greedy and self.logits.is_cuda and self.logits.stride(-1) == 1:
             from . import fused_ops
             fused_ops.greedy_advance(self.logits, self.tok, self.write_index, self.pos, self.mask)   # one launch
+            if lp:
+                fused_ops.step_logprobs(self.logits, self.tok.view(-1), self.lp)
             return
         if greedy:
             self.tok.copy_(self.logits.argmax(dim=-1, keepdim=True))
+            if lp:                                              # (CPU: the host form)
+                from . import fused_ops
+                fused_ops.step_logprobs(self.logits, self.tok.view(-1), self.lp)
         self.write_index.add_(1)
         self.pos.add_(1)
         self.mask.index_fill_(2, torch.clamp(self.write_index, max=self.capacity - 1), 0.0)
@@ -417,28 +474,34 @@ class DecodeSession:
         return tuple(key)
 
     @staticmethod
-    def _mode(greedy: bool, sample: bool, rows: bool = False, pen: bool = False) -> str:
+    def _mode(greedy: bool, sample: bool, rows: bool = False, pen: bool = False, lp: bool = False) -> str:
         mode = "rows" if rows else ("sample" if sample else ("greedy" if greedy else "logits"))
-        return mode + "+pen" if pen and mode != "logits" else mode   # "greedy+pen", "sample+pen", "rows+pen": graphs of their own
+        if mode == "logits":                                    # the host decides: it adjusts and records what it gets back
+            return mode
+        # "greedy+pen", "sample+lp", "rows+pen+lp", ...: graphs of their own
+        return mode + ("+pen" if pen else "") + ("+lp" if lp else "")
 
     @property
     def _captured_greedy(self):                                 # kept for the developer tools that read it
         return self._captured_mode == "greedy"
 
     @torch.no_grad()
-    def capture(self, greedy: bool = True, sample: bool = False, rows: bool = False, pen: bool = False):
+    def capture(self, greedy: bool = True, sample: bool = False, rows: bool = False, pen: bool = False, lp: bool = False):
         """Capture one decode step of the mode - "sample": the device sampler picks the next token, "greedy": the argmax does,
         "rows": the batched generation's per-row kernel does (arm_rows), "logits": the host decides - or keep the captured one while nothing it bakes in has changed.  Graphs of several modes live
         side by side (a decoder that alternates greedy and sampled generations captures each once).  ``pen``: the step with the sampling
         controls' launch (arm_penalties) between lm_head and the selection - "greedy+pen" / "sample+pen" / "rows+pen", captured
-        next to the plain ones, which stay as they are."""
+        next to the plain ones, which stay as they are.  ``lp``: the step with the log-prob record's launch (arm_logprobs) behind the
+        selection - "greedy+lp", "rows+pen+lp", ... - again graphs of their own."""
         if not self.use_graph:
             return
         from . import _lib
-        mode = self._mode(greedy, sample, rows, pen)
-        pen = mode.endswith("+pen")
+        mode = self._mode(greedy, sample, rows, pen, lp)
+        pen, lp = "+pen" in mode, mode.endswith("+lp")
         if pen and self.pen is None:
             raise RuntimeError("capture(pen=True) before arm_penalties")
+        if lp and self.lp is None:
+            raise RuntimeError("capture(lp=True) before arm_logprobs")
         if self._graphs:
             # cheap test first (a process-wide counter every derived-layout build / drop bumps), the full fingerprint when it moved
             valid = self._graph_epoch == _lib.layout_epoch() and self._graph_versions == self._canonical_versions()
@@ -454,26 +517,28 @@ class DecodeSession:
                 return
         if self.decode_only:
             self.release_prefill_layouts()
-        # (the token counts of the sampling controls included: the warm-up runs must not count tokens)
-        state = (self.tok, self.write_index, self.pos, self.mask, self.rng_state) + self.rows.tensors() + (self.pen.tensors() if pen else ())
+        # (the token counts of the sampling controls included: the warm-up runs must not count tokens; and the log-prob record's
+        # entry counts: they must record nothing - what they wrote past the count is overwritten by the steps that follow)
+        state = ((self.tok, self.write_index, self.pos, self.mask, self.rng_state) + self.rows.tensors()
+                 + (self.pen.tensors() if pen else ()) + ((self.lp.count,) if lp else ()))
         saved = tuple(t.clone() for t in state)
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
-            self._step_body(greedy, sample, rows, pen)          # warm-up: allocations, lazy repacks
+            self._step_body(greedy, sample, rows, pen, lp)          # warm-up: allocations, lazy repacks
             # the warm-up built what the step reads (e.g. the gate-interleaved copy of w_in): what it made redundant goes now,
             # and the step runs once more so that every pre-bound launch exists before the capture
             if self.decode_only and self.release_prefill_layouts():
-                self._step_body(greedy, sample, rows, pen)
+                self._step_body(greedy, sample, rows, pen, lp)
             if self.low_footprint and self.drop_canonical():
-                self._step_body(greedy, sample, rows, pen)      # the pre-bound launches re-validate against the stand-in buffers
+                self._step_body(greedy, sample, rows, pen, lp)      # the pre-bound launches re-validate against the stand-in buffers
         torch.cuda.current_stream(self.device).wait_stream(side)
         if self._graphs and self._graph_epoch != _lib.layout_epoch():
             self._graphs.clear()                                # this mode's warm-up rebuilt / dropped a layout the older graphs baked in
             self._graph_logits.clear()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            self._step_body(greedy, sample, rows, pen)
+            self._step_body(greedy, sample, rows, pen, lp)
         # capture ran the body twice on live state: restore (the cache rows it touched get rewritten)
         for dst, src in zip(state, saved):
             dst.copy_(src)
@@ -509,26 +574,28 @@ class DecodeSession:
 
     @torch.no_grad()
     def decode_step(self, token: Optional[Tensor] = None, greedy: bool = True, sample: bool = False, rows: bool = False,
-                    pen: bool = False) -> Tensor:
+                    pen: bool = False, lp: bool = False) -> Tensor:
         """Advance by one token.  `token` (batch, 1) overrides the device-resident next id (needed when the
         host samples).  ``sample``: the device sampler (set_sampling) draws the next id into ``tok``.  Returns this step's
         last-position logits (batch, vocab).  ``rows``: the batched generation's step (arm_rows): every row selects, records and
         stops on its own; returns None (the tokens are in ``rows.out_tokens``).  ``pen``: the armed sampling controls (arm_penalties)
         count the id fed into the step and adjust the logits in front of the selection; the host-decides mode (neither greedy, sample
-        nor rows) returns the logits as the model gave them - its caller adjusts them (``fused_ops.logit_penalties``)."""
+        nor rows) returns the logits as the model gave them - its caller adjusts them (``fused_ops.logit_penalties``).  ``lp``: the
+        armed log-prob record (arm_logprobs) gets this step's entry behind the selection; the host-decides mode records nothing -
+        its caller does, with the id it chose (``fused_ops.step_logprobs``)."""
         if self.length + 1 > self.capacity:
             raise ValueError("cache capacity exhausted")
         if token is not None:
             self.tok.copy_(token.to(self.device))
-        mode = self._mode(greedy, sample, rows, pen)
-        pen = mode.endswith("+pen")
+        mode = self._mode(greedy, sample, rows, pen, lp)
+        pen, lp = "+pen" in mode, mode.endswith("+lp")
         if mode in self._graphs:
             from . import _lib
             if self._graph_epoch != _lib.layout_epoch() or self._captured_mode != mode:   # a derived layout was rebuilt / dropped since
-                self.capture(greedy, sample, rows, pen)         # the capture: capture() compares the fingerprint and keeps the graphs
+                self.capture(greedy, sample, rows, pen, lp)     # the capture: capture() compares the fingerprint and keeps the graphs
             self.graph.replay()                                 # when only modules of OTHER models / sessions moved (ADVICE r3)
         else:
-            self._step_body(greedy, sample, rows, pen)
+            self._step_body(greedy, sample, rows, pen, lp)
         self.length += 1
         self.cache.length = self.length
         return None if rows else self.logits
@@ -594,6 +661,9 @@ class ChatGLMDecoder:
         self.max_sequence_length = max_sequence_length or model.config.max_sequence_length
         self.time_log = time_log
         self.last_stats: dict = {}
+        # what the last generation with ``logprobs=n`` recorded: one GenerationLogprobs (generate_ids) or a list of them in prompt
+        # order (generate_batch_ids); None after a generation without
+        self.last_logprobs = None
 
     @staticmethod
     def from_pretrained(path, device=None, torch_dtype=None, tokenizer=None, eos_token: str = "</s>", time_log: bool = False,
@@ -755,7 +825,8 @@ class ChatGLMDecoder:
                      top_p: float = 0.8, temperature: float = 1.0, greedy: bool = False, ignore_eos: bool = False,
                      prefill_chunk: Optional[int] = None, use_graph: Optional[bool] = None, sync_every_token: bool = True,
                      seed: Optional[int] = None, device_sampler: Optional[bool] = None, repetition_penalty: float = 1.0,
-                     presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias: Optional[dict] = None):
+                     presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias: Optional[dict] = None,
+                     logprobs: Optional[int] = None):
         """Yields generated token ids one by one (batch 1, like the reference, chatglm_q/decoder.py:70).
 
         Default = the reference's only mode: top-k / top-p sampling (top_k 100, top_p 0.8, temperature 1.0).  On a GPU the
@@ -769,11 +840,22 @@ class ChatGLMDecoder:
         and ``frequency_penalty`` f subtract p + f x (times generated) from the logit of every id generated so far (OpenAI's
         rule); ``logit_bias`` ``{id: value}`` (at most ``fused_ops.LOGIT_BIAS_MAX`` entries, values finite or -inf: -inf bans the
         id) is added last.  They run as one more launch inside the captured step, in front of the argmax / the sampler, on the
-        history kept on the device; ``last_stats["penalties"]`` says whether they were active."""
+        history kept on the device; ``last_stats["penalties"]`` says whether they were active.
+
+        ``logprobs`` (None: off, the path above exactly): an int n in [0, ``fused_ops.TOP_LOGPROBS_MAX``] records every generated
+        token's log-probability and the n most likely ids of its step with theirs - under the logits the selection read, after the
+        sampling controls, before temperature / top-k / top-p - by one more launch behind the selection inside the captured step.
+        The ids are yielded as before; when the generation ends (or the generator is closed) ``last_logprobs`` holds a
+        ``GenerationLogprobs`` with one entry per token yielded, read from the device once; ``last_stats["logprobs"]`` says whether
+        the record was on."""
+        n_lp = check_logprobs(logprobs)
+        self.last_logprobs = None
         prefix = list(prefix_ids)
         limit = min(self.max_sequence_length, self.model.config.max_sequence_length)   # the cache cannot outgrow the rotary table
         budget = min(max_generated_tokens, limit - len(prefix))
         if budget <= 0:
+            if n_lp is not None:
+                self.last_logprobs = GenerationLogprobs([], [], [])
             return
         capacity = min(-(-(len(prefix) + budget) // 64) * 64, self.model.config.max_sequence_length)
         sess = self._session_for(capacity, use_graph)
@@ -787,15 +869,30 @@ class ChatGLMDecoder:
                 if seed is None:
                     seed = int(torch.randint(0, 2 ** 62, (1,)).item())
                 sess.set_sampling(top_k, top_p, temperature, seed)
-            yield from self._generate(sess, prefix, budget, top_k, top_p, temperature, greedy, ignore_eos, prefill_chunk,
-                                      sync_every_token, dev_sample, pen)
+            if n_lp is None:
+                yield from self._generate(sess, prefix, budget, top_k, top_p, temperature, greedy, ignore_eos, prefill_chunk,
+                                          sync_every_token, dev_sample, pen)
+            else:
+                sess.arm_logprobs(True)
+                returned = 0
+                inner = self._generate(sess, prefix, budget, top_k, top_p, temperature, greedy, ignore_eos, prefill_chunk,
+                                       sync_every_token, dev_sample, pen, lp=True)
+                try:
+                    for token in inner:
+                        returned += 1
+                        yield token
+                finally:
+                    inner.close()
+                    # one read at the end, cut to the tokens handed out (the ahead-launch records one step past an end token)
+                    self.last_logprobs = GenerationLogprobs(*sess.lp.read(0, n_lp, limit=returned))
         finally:
             sess.busy = False
             if POST_GENERATE_CHECK is not None:                 # set by chatglm_q_amd.dev.experiments: error words of one-launch MLPs
                 POST_GENERATE_CHECK(sess)
 
     def _generate(self, sess: DecodeSession, prefix, budget: int, top_k: int, top_p: float, temperature: float, greedy: bool,
-                  ignore_eos: bool, prefill_chunk: Optional[int], sync_every_token: bool, dev_sample: bool = False, pen: bool = False):
+                  ignore_eos: bool, prefill_chunk: Optional[int], sync_every_token: bool, dev_sample: bool = False, pen: bool = False,
+                  lp: bool = False):
         # `auto`: the device picks the next token inside the step (argmax or the one-launch sampler) and feeds it back itself
         auto = greedy or dev_sample
         times = []
@@ -809,6 +906,10 @@ class ChatGLMDecoder:
             nxt = sess.sample_first(logits)
         else:
             nxt = logits.argmax(-1) if greedy else top_p_sampling(logits, top_k, top_p, temperature)
+            if lp:
+                sess.tok.copy_(nxt.view(-1, 1))                    # the record reads the chosen id from device memory
+        if lp:
+            sess.logprobs_first(logits)
         token = int(nxt.item())                                    # the sync that makes the timing valid
         times.append(time.perf_counter() - t0)
         generated = [token]
@@ -817,7 +918,7 @@ class ChatGLMDecoder:
         device_loop = auto and not sync_every_token and (ignore_eos or self.eos_token_id is None)
         if len(generated) < budget and (ignore_eos or token != self.eos_token_id):
             sess.tok.fill_(token)
-            sess.capture(greedy=greedy, sample=dev_sample, pen=pen)
+            sess.capture(greedy=greedy, sample=dev_sample, pen=pen, lp=lp)
         pending = []
         # Greedy or device-sampled decoding on a captured step: the graph feeds its own choice back, so step k + 1 does not wait for the HOST to have seen
         # token k.  It is launched before token k is read (one step of speculation: wasted - and harmless, the next prefill re-arms the
@@ -830,7 +931,7 @@ class ChatGLMDecoder:
             events = [torch.cuda.Event(), torch.cuda.Event()]
 
             def launch(k):
-                sess.decode_step(None, greedy=greedy, sample=dev_sample, pen=pen)
+                sess.decode_step(None, greedy=greedy, sample=dev_sample, pen=pen, lp=lp)
                 ring[k & 1].copy_(sess.tok.view(-1), non_blocking=True)
                 events[k & 1].record()
 
@@ -855,16 +956,20 @@ class ChatGLMDecoder:
             t0 = time.perf_counter()
             if device_loop:
                 # the graph feeds its own choice back as the next input: the host only replays
-                sess.decode_step(greedy=greedy, sample=dev_sample, pen=pen)
+                sess.decode_step(greedy=greedy, sample=dev_sample, pen=pen, lp=lp)
                 pending.append(sess.tok.clone())
                 generated.append(-1)
                 times.append(time.perf_counter() - t0)
                 continue
-            logits = sess.decode_step(None if auto else torch.tensor([[generated[-1]]]), greedy=greedy, sample=dev_sample, pen=pen)
+            logits = sess.decode_step(None if auto else torch.tensor([[generated[-1]]]), greedy=greedy, sample=dev_sample, pen=pen,
+                                      lp=lp)
             if pen and not auto:                                   # the host samples: it adjusts the logits it got back (tok = the id just fed)
                 from . import fused_ops
                 logits = fused_ops.logit_penalties(logits if logits.stride(-1) == 1 else logits.contiguous(), sess.pen, sess.tok.view(-1))
             nxt = sess.tok[:, 0] if auto else top_p_sampling(logits, top_k, top_p, temperature)
+            if lp and not auto:                                    # ... and records its own choice on the logits it sampled from
+                from . import fused_ops
+                fused_ops.step_logprobs(logits, nxt.view(-1).contiguous(), sess.lp)
             token = int(nxt.item())
             times.append(time.perf_counter() - t0)
             generated.append(token)
@@ -883,7 +988,7 @@ class ChatGLMDecoder:
         self.last_stats = {
             "prefix": len(prefix), "generated": n, "init_s": times[0], "sum_s": sum(times),
             "gen_tok_per_s": (n - 1) / rest if n > 1 and rest > 0 else float("nan"),
-            "avg_tok_per_s": n / sum(times), "penalties": bool(pen),
+            "avg_tok_per_s": n / sum(times), "penalties": bool(pen), "logprobs": bool(lp),
         }
         if self.time_log:
             s = self.last_stats
@@ -916,7 +1021,7 @@ class ChatGLMDecoder:
     def generate_batch_ids(self, prompts, max_generated_tokens=400, top_k=100, top_p=0.8, temperature=1.0, greedy=False,
                            seed=None, ignore_eos: bool = False, prefill_chunk: Optional[int] = None, use_graph: Optional[bool] = None,
                            poll_every: Optional[int] = None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
-                           logit_bias=None):
+                           logit_bias=None, logprobs: Optional[int] = None):
         """Generate for a batch of prompts (lists of token ids, any lengths: LEFT padded with 0 as ``score_ids`` pads them) in one
         decode batch; returns one list of generated ids per prompt.  A row that stopped on the end token ends with it, as
         ``generate_ids`` yields it.
@@ -938,7 +1043,13 @@ class ChatGLMDecoder:
         ``generate_ids``' sampling controls, each a scalar / one dict or one per prompt.  A row's history is its own prompt (the pads
         in front of it are no prompt tokens) and its own tokens; the controls run as one more launch in the captured step, so a
         row's tokens still do not depend on its batch position or on its neighbours' settings.  Defaults: off, the path above
-        exactly; ``last_stats["penalties"]`` says whether they were active."""
+        exactly; ``last_stats["penalties"]`` says whether they were active.
+
+        ``logprobs`` (None: off) is ``generate_ids``' as well: with an int n in [0, ``fused_ops.TOP_LOGPROBS_MAX``] the step records
+        every row's token log-prob and n alternatives on the device (finished rows record nothing), and ``last_logprobs`` holds one
+        ``GenerationLogprobs`` per prompt, in prompt order, each as long as the row's returned ids."""
+        n_lp = check_logprobs(logprobs)
+        self.last_logprobs = None
         prompts = [list(map(int, p)) for p in prompts]
         if not prompts or any(len(p) == 0 for p in prompts):
             raise ValueError("generate_batch_ids: at least one prompt, none of them empty")
@@ -980,7 +1091,10 @@ class ChatGLMDecoder:
                     per_row("frequency_penalty", frequency_penalty, float), per_row("logit_bias", logit_bias, lambda d: d))
         fused_ops.PenaltyState.check(B, self.model.config.vocab_size, list(zip(*pen_args[:3])), pen_args[3])
         if max(budgets) == 0:
-            self.last_stats = {"batch": B, "prefix": [len(p) for p in prompts], "generated": [0] * B, "steps": 0, "penalties": False}
+            self.last_stats = {"batch": B, "prefix": [len(p) for p in prompts], "generated": [0] * B, "steps": 0, "penalties": False,
+                               "logprobs": n_lp is not None}
+            if n_lp is not None:
+                self.last_logprobs = [GenerationLogprobs([], [], []) for _ in prompts]
             return [[] for _ in prompts]
         ids = torch.zeros((B, S), dtype=torch.long)
         attn = torch.zeros((B, S), dtype=torch.long)
@@ -994,17 +1108,20 @@ class ChatGLMDecoder:
         try:
             sess.arm_rows(list(zip(ks, ps, ts)), seeds, budgets, stop)
             pen = sess.arm_penalties(prompts, *pen_args)
+            lp = sess.arm_logprobs(n_lp is not None)
             cuda = sess.device.type == "cuda"
             t0 = time.perf_counter()
             logits = sess.prefill(ids, prefill_chunk, attention_mask=attn)
             if pen:
                 logits = sess.penalize_first(logits, rows=True)
             sess.sample_rows_first(logits)
+            if lp:
+                sess.logprobs_first(logits, rows=True)
             live = int(sess.rows.live.item())                   # the sync that makes the first-token time valid
             t_first = time.perf_counter() - t0
             steps, max_steps = 0, max(budgets) - 1
             if live > 0 and max_steps > 0:
-                sess.capture(greedy=False, rows=True, pen=pen)
+                sess.capture(greedy=False, rows=True, pen=pen, lp=lp)
                 if cuda:
                     ring = torch.zeros((2, 1 + 2 * B), dtype=torch.int32).pin_memory()
                     events = [torch.cuda.Event(), torch.cuda.Event()]
@@ -1012,7 +1129,7 @@ class ChatGLMDecoder:
                 while steps < max_steps:
                     n = min(poll, max_steps - steps)
                     for _ in range(n):
-                        sess.decode_step(greedy=False, rows=True, pen=pen)
+                        sess.decode_step(greedy=False, rows=True, pen=pen, lp=lp)
                     steps += n
                     if not cuda:
                         if int(sess.rows.live[0]) == 0:
@@ -1030,10 +1147,13 @@ class ChatGLMDecoder:
             out = sess.rows.out_tokens.cpu()                    # one copy of the tokens at the end
             state = sess.rows.row_state.cpu()
             total = time.perf_counter() - t0
+            record = sess.lp.fetch() if lp else None            # ... and one of every buffer of the log-prob record
         finally:
             sess.busy = False
         counts = [int(state[b, 0]) for b in range(B)]
         res = [out[b, :counts[b]].tolist() for b in range(B)]
+        if lp:
+            self.last_logprobs = [GenerationLogprobs(*sess.lp.read(b, n_lp, limit=counts[b], host=record)) for b in range(B)]
         gen = sum(counts)
         rest = total - t_first
         self.last_stats = {
@@ -1041,7 +1161,7 @@ class ChatGLMDecoder:
             "invalid": [b for b in range(B) if int(state[b, 1]) & fused_ops.BatchRows.INVALID],
             "prefill_s": t_first, "sum_s": total,
             "gen_tok_per_s": (gen - sum(1 for c in counts if c)) / rest if steps and rest > 0 else float("nan"),
-            "avg_tok_per_s": gen / total if total > 0 else float("nan"), "penalties": bool(pen),
+            "avg_tok_per_s": gen / total if total > 0 else float("nan"), "penalties": bool(pen), "logprobs": bool(lp),
         }
         if self.time_log:
             s = self.last_stats

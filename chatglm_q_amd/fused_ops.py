@@ -720,6 +720,111 @@ def logit_penalties(logits: Tensor, state: PenaltyState, tok: Tensor | None = No
     return logits
 
 
+# ---- log-probabilities during generation: the chosen token's and the most likely alternatives' (csrc/logprob.hip) -------------------------
+TOP_LOGPROBS_MAX = 20        # alternatives one step can record (QL_TOP_LOGPROBS_MAX, include/qlinear_hip.h)
+
+
+class StepLogprobs:
+    """The record ``step_logprobs`` appends to (static device buffers a captured step reads and updates): ``count`` (batch,) int32 =
+    entries recorded per row; ``chosen`` (batch, cap) float32 = log-prob of every recorded token; ``top_ids`` / ``top_lp`` (batch,
+    cap, n_top) int32 / float32 = the ``n_top`` most likely ids of that step (value descending, ties: lowest index first) and their
+    log-probs.  The width ``n_top`` defaults to TOP_LOGPROBS_MAX, so one captured graph serves every number of alternatives asked
+    for; ``read`` slices."""
+
+    def __init__(self, batch: int, cap: int, device, n_top: int = TOP_LOGPROBS_MAX):
+        if batch < 1 or cap < 1 or not 0 <= n_top <= TOP_LOGPROBS_MAX:
+            raise ValueError(f"StepLogprobs: batch >= 1, cap >= 1, 0 <= n_top <= {TOP_LOGPROBS_MAX} (got {batch}, {cap}, {n_top})")
+        self.batch, self.cap, self.n_top, self.device = batch, cap, n_top, torch.device(device)
+        self.count = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.chosen = torch.zeros((batch, cap), dtype=torch.float32, device=device)
+        self.top_ids = torch.zeros((batch, cap, n_top), dtype=torch.int32, device=device)
+        self.top_lp = torch.zeros((batch, cap, n_top), dtype=torch.float32, device=device)
+
+    def arm(self):
+        """Start a generation: nothing recorded (the buffers keep their addresses and, past ``count``, their old contents)."""
+        self.count.zero_()
+        return self
+
+    def tensors(self):
+        return (self.count, self.chosen, self.top_ids, self.top_lp)
+
+    def fetch(self):
+        """The whole record on the host, one copy per buffer: what ``read`` slices (pass it as ``host`` when reading several rows)."""
+        return tuple(t.cpu() for t in self.tensors())
+
+    def read(self, b: int, n: int | None = None, limit: int | None = None, host=None):
+        """Row b's first ``min(count[b], limit)`` entries with ``n`` alternatives each (default: all ``n_top``), as lists:
+        ``(token_logprobs, top_ids, top_logprobs)``."""
+        n = self.n_top if n is None else int(n)
+        if not 0 <= n <= self.n_top:
+            raise ValueError(f"StepLogprobs.read: 0 <= n <= {self.n_top} (got {n})")
+        count, chosen, ids, lps = self.fetch() if host is None else host
+        k = min(int(count[b]), self.cap)
+        if limit is not None:
+            k = min(k, max(0, int(limit)))
+        return chosen[b, :k].tolist(), ids[b, :k, :n].tolist(), lps[b, :k, :n].tolist()
+
+
+def _step_logprobs_host(logits: Tensor, tok: Tensor, state: StepLogprobs, row_state):
+    """CPU form of qlinear_step_logprobs: the same rules, torch's fp32 log_softmax and a stable descending sort for the order."""
+    B, N = logits.shape
+    n_top = state.n_top
+    k = min(n_top, N)
+    xf = logits.float()
+    lsm_rows = torch.log_softmax(xf, dim=-1)                     # the call token_logprob's CPU branch makes
+    for b in range(B):
+        c = int(state.count[b])
+        if row_state is not None and int(row_state[b, 0]) <= c:
+            continue                                             # the row recorded no token in this step
+        if c >= state.cap:
+            continue
+        x, lsm = xf[b], lsm_rows[b]
+        t = int(tok[b])
+        state.chosen[b, c] = lsm[t] if 0 <= t < N else float("nan")
+        if n_top:
+            order = torch.sort(torch.where(torch.isnan(x), torch.full_like(x, float("-inf")), x), descending=True, stable=True)[1][:k]
+            state.top_ids[b, c, :k] = order.to(torch.int32)
+            state.top_lp[b, c, :k] = lsm[order]
+            state.top_ids[b, c, k:] = -1
+            state.top_lp[b, c, k:] = float("-inf")
+        state.count[b] = c + 1
+
+
+def step_logprobs(logits: Tensor, tok: Tensor, state: StepLogprobs, row_state: Tensor | None = None) -> None:
+    """Record one generation step in ``state`` (``qlinear_step_logprobs``, one launch behind the step's selection; its comment in
+    include/qlinear_hip.h holds the rules): for every row of `logits` (B, N) - the row the selection read - the log-prob of the id
+    just chosen, ``tok`` (B,) int64, and the ``state.n_top`` most likely ids with theirs, appended at ``state.count[b]``.
+    ``row_state``: a ``BatchRows.row_state``; a row whose token count has not moved past its recorded entries (finished, out of
+    budget) records nothing.  A full record (``state.cap`` entries) records nothing either.  On a GPU every value is bit-equal to
+    ``token_logprob(logits, that id)``.  CPU tensors take the host form (torch ops, the same rules)."""
+    if logits.dim() != 2 or logits.shape[1] < 1:
+        raise ValueError(f"step_logprobs: logits must be (B, N) with N >= 1, got {tuple(logits.shape)}")
+    B, N = logits.shape
+    if B != state.batch:
+        raise ValueError(f"step_logprobs: {B} logits rows for a StepLogprobs of {state.batch}")
+    if tok.dtype != torch.int64 or tok.numel() != B or not tok.is_contiguous():
+        raise ValueError("step_logprobs: tok must be a contiguous int64 tensor of B elements")
+    if row_state is not None and (row_state.dtype != torch.int32 or tuple(row_state.shape) != (B, 2) or not row_state.is_contiguous()):
+        raise ValueError("step_logprobs: row_state must be a contiguous int32 (B, 2) tensor (BatchRows.row_state)")
+    for t in (tok, row_state) + state.tensors():
+        if t is not None and t.device != logits.device:
+            raise ValueError(f"step_logprobs: logits on {logits.device}, state on {t.device}")
+    if not logits.is_cuda:
+        _step_logprobs_host(logits, tok.view(-1), state, row_state)
+        return None
+    lib = _lib.get_lib()
+    if logits.stride(1) != 1 or (B > 1 and logits.stride(0) < N):
+        logits = logits.contiguous()
+    n_top = state.n_top
+    with torch.cuda.device(logits.device):
+        st = lib.qlinear_step_logprobs(logits.data_ptr(), B, N, logits.stride(0) if B > 1 else N, tok.data_ptr(), _lib.ptr(row_state),
+                                       state.count.data_ptr(), state.chosen.data_ptr(), state.top_ids.data_ptr() if n_top else None,
+                                       state.top_lp.data_ptr() if n_top else None, state.cap, n_top, _lib.dtype_code(logits.dtype),
+                                       _lib.stream_ptr(logits.device))
+    _lib.check(st, "qlinear_step_logprobs")
+    return None
+
+
 # ---- GPTQ: the column walk of one block (csrc/gptq.hip) ------------------------------------------------------------------------------
 GPTQ_MAX_BLOCK = 128
 

@@ -50,7 +50,9 @@ extern "C" {
  * Still 3: qlinear_batch_sample_advance added - purely additive as well.
  * Still 3: qlinear_logit_penalties (and the constant QL_LOGIT_BIAS_MAX) added - purely additive; the selection entry points
  * (qlinear_greedy_advance, qlinear_top_p_sample, qlinear_batch_sample_advance) are unchanged, they read the adjusted logits.
- * Still 3: qlinear_gptq_block added - purely additive. */
+ * Still 3: qlinear_gptq_block added - purely additive.
+ * Still 3: qlinear_step_logprobs (and the constant QL_TOP_LOGPROBS_MAX) added - purely additive; qlinear_token_logprob and the
+ * selection entry points are unchanged. */
 #define QLINEAR_ABI_VERSION 3
 
 /* activation dtypes */
@@ -561,6 +563,36 @@ int qlinear_batch_sample_advance(const void* logits, int64_t B, int64_t N, int64
 int qlinear_logit_penalties(void* logits, int64_t B, int64_t N, int64_t ldl, const float* settings, const int32_t* bias_ids,
                             const float* bias_vals, const int32_t* bias_len, int64_t bias_cap, int32_t* state, int64_t lds,
                             const int64_t* tok, const int32_t* row_state, int dtype, void* stream);
+
+/* Per-token log-probabilities DURING generation: one launch behind a step's selection entry point (qlinear_greedy_advance,
+ * qlinear_top_p_sample or qlinear_batch_sample_advance - tok[b] already holds the id just chosen) that reads the logits row the
+ * selection read (after qlinear_logit_penalties, before temperature / top-k / top-p) and appends, per row, the log-probability of
+ * the chosen id and the n_top most likely ids with theirs to a record in device memory - the host reads it once at the end.
+ *   tok (B) int64: the id chosen this step.  row_state (B, 2) int32, nullable: qlinear_batch_sample_advance's.
+ *   count (B) int32: entries recorded so far per row.  chosen (B, cap) float.  top_ids / top_lp (B, cap, n_top) int32 / float
+ *   (nullable when n_top == 0).  0 <= n_top <= QL_TOP_LOGPROBS_MAX, cap >= 1.
+ * For row b, c = count[b]:
+ *   skip:  row_state given and row_state[b][0] <= c - the row recorded no token in this step (it is finished, or its budget ran
+ *          out): nothing is written.  (While a row is live its count trails its token count by exactly one at this point.)
+ *   full:  c >= cap: nothing is written, count stays.
+ *   otherwise, x = float(logits[b][:]), m = the row maximum, s = sum exp(x - m), computed exactly as qlinear_token_logprob's
+ *   1024-thread kernel computes them (same chunk ownership, same arithmetic, same merge):
+ *     chosen[b][c] = (x[tok[b]] - m) - log(s)            NaN when tok[b] is outside [0, N)
+ *     top_ids[b][c][j], top_lp[b][c][j], j < min(n_top, N): the j-th entry of the row under the strict total order (value descending,
+ *       index ascending - qlinear_top_p_sample's order; a NaN logit ranks as -inf) and its (x_j - m) - log(s);  j >= N: -1, -inf
+ *     count[b] = c + 1
+ *   so for B < 1024 every value written is BIT-EQUAL to what qlinear_token_logprob returns for the same row with that id as target.
+ * The selection is exact for every row; rows whose candidate list would overflow (a sorted row, a row of mostly -inf, a tie group
+ * of more than 1024 at the cut) take a slow path of n_top workgroup arg-max rounds.  One workgroup of 1024 threads per row; any
+ * N >= 1; logits aligned to its element size only; nothing outside [row, row + N) is read; every output element has one owner,
+ * plain vector loads and stores.
+ * QL_ERR_BAD_DTYPE; QL_ERR_BAD_SHAPE for N < 1, ldl < N, B > 65535, cap < 1 or n_top outside [0, QL_TOP_LOGPROBS_MAX];
+ * QL_ERR_NULL_POINTER for a missing logits / tok / count / chosen (or a missing top array with n_top > 0); QL_ERR_MISALIGNED for
+ * logits not aligned to the element size; B == 0 is QL_OK without a launch. */
+#define QL_TOP_LOGPROBS_MAX 20
+int qlinear_step_logprobs(const void* logits, int64_t B, int64_t N, int64_t ldl, const int64_t* tok, const int32_t* row_state,
+                          int32_t* count, float* chosen, int32_t* top_ids, float* top_lp, int64_t cap, int64_t n_top, int dtype,
+                          void* stream);
 
 /* GPTQ (chatglm_q/int4/quantizer.py:151-167, chatglm_q/int8/quantizer.py:126-137): the column walk of ONE block of bc <= 128 input
  * columns over all weight rows in one launch.  All arrays fp32 device memory (dtype must be QL_DTYPE_F32).
