@@ -59,6 +59,7 @@ EXPORTS = {
     "qlinear_status_string": (c_char_p, [c_int]),
     "qlinear_launch_count": (c_uint64, []),
     "qlinear_last_dispatch": (c_uint64, []),
+    "qlinear_w4g32_onetile_launches": (c_uint64, []),
     "qlinear_dispatch_reset": (None, []),
     "qlinear_dispatch_reload": (None, []),
     "qlinear_dispatch_flags": (ctypes.c_uint, []),

@@ -32,6 +32,7 @@ static unsigned parse_dispatch_env() {
     if (strstr(e, "norows16")) v |= QL_D_NOROWS16;
     if (strstr(e, "norows4")) v |= QL_D_NOROWS4;
     if (strstr(e, "nogroupattn")) v |= QL_D_NOGROUPATTN;
+    if (strstr(e, "noonetile")) v |= QL_D_NOONETILE;
     return v;
 }
 static std::atomic<unsigned> g_dispatch{0};
@@ -92,6 +93,8 @@ const char* qlinear_status_string(int status) {
 }
 
 uint64_t qlinear_launch_count(void) { return g_launches.load(std::memory_order_relaxed); }
+
+uint64_t qlinear_w4g32_onetile_launches(void) { return w4_gemv_onetile_launches(); }
 
 uint64_t qlinear_last_dispatch(void) { return t_dispatch_log; }
 void qlinear_dispatch_reset(void) { t_dispatch_log = 0; }

@@ -23,9 +23,10 @@ inline int tune_env(const char* name, int dflt) {
 // the same function): "no256" (256 x 256-tile GEMMs), "nopeel" (qkv_proj's second launch on the 128-row-tile kernel),
 // "nofewrow" (3..32-row kernels), "norows4" (4x4x4-MFMA kernel for 2..4 rows), "nogroupattn" (grouped MFMA decode attention),
 // "nohalf" (round 5: the half-tile last round of the int4g32 256-tile GEMM's launch; whole tiles only, the older peel where it applies -
-// the rows both serve are bit-equal), "nof32mfma" (round 5: the fp32 matrix-instruction kernel for fp32 activations with 128+ rows; the VALU kernels instead).
+// the rows both serve are bit-equal), "nof32mfma" (round 5: the fp32 matrix-instruction kernel for fp32 activations with 128+ rows; the VALU kernels instead),
+// "noonetile" (the straight-line one-row int4g32 GEMV for K slices of one 64-group tile: the tile-loop kernel instead, bit-equal).
 enum : unsigned { QL_D_NO256 = 1, QL_D_NOPEEL = 2, QL_D_NOFEWROW = 4, QL_D_NOROWS4 = 8, QL_D_NOGROUPATTN = 16, QL_D_NOHALF = 32,
-                  QL_D_NOF32MFMA = 64, QL_D_NOROWS16 = 128 };
+                  QL_D_NOF32MFMA = 64, QL_D_NOROWS16 = 128, QL_D_NOONETILE = 256 };
 unsigned dispatch_flags();     // abi.hip: parsed once; qlinear_dispatch_reload() parses again (tests, A/B tools)
 
 }  // namespace ql

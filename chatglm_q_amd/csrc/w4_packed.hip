@@ -19,6 +19,8 @@
 // queue so that their s_waitcnt does not drain the weight loads behind them.
 #include <stdlib.h>
 
+#include <atomic>
+
 #include "launch.h"
 #include "w4_dequant.h"
 #include "w4_splice.h"
@@ -168,6 +170,33 @@ __device__ unsigned long long ql_span_slots[2 * kSpanWaves];
 #define QL_SPAN_END() do { } while (0)
 #endif
 
+// QL_TIMELINE_PROBE (developer build `make timeline`, never in libqlinear_hip.so; tools/gemv_onetile_timeline.py): every wave of the
+// 16-bit GEMV stamps s_memrealtime at seven stations - 0 entry, 1 staging barrier passed, 2 last weight word landed, 3 dots done,
+// 4 reductions done, 5 K-slice barrier passed, 6 store issued - and lane 0 writes them, with the wave's HW_ID / XCC_ID registers (which CU
+// it ran on), into the wave's own slot by plain stores at the very end.  A stamp is held in place by the values it follows
+// (QL_TL_DEP: an empty asm that consumes them); station 2 waits for the vector-memory queue itself, where the kernel waits anyway.
+#ifdef QL_TIMELINE_PROBE
+constexpr int kTlWaves = 1 << 13, kTlWords = 8;
+__device__ unsigned long long ql_tl_slots[kTlWords * kTlWaves];
+#define QL_TL_DECL() unsigned long long tl_t[7] = {0, 0, 0, 0, 0, 0, 0}
+#define QL_TL(i) do { tl_t[i] = (unsigned long long)__builtin_amdgcn_s_memrealtime(); } while (0)
+#define QL_TL_DEP(x) asm volatile("" ::"v"(x))
+#define QL_TL_LANDED() do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); QL_TL(2); } while (0)
+#define QL_TL_WRITE() do { \
+        if ((threadIdx.x & 63) == 0) { \
+            unsigned long long* tl_p = ql_tl_slots + (size_t)kTlWords * (((int)(by * gridDim.x + bx) * 4 + (int)(threadIdx.x >> 6)) & (kTlWaves - 1)); \
+            _Pragma("unroll") for (int tl_i = 0; tl_i < 7; ++tl_i) tl_p[tl_i] = tl_t[tl_i]; \
+            tl_p[7] = (unsigned long long)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11)) | \
+                      ((unsigned long long)__builtin_amdgcn_s_getreg((20) | (0 << 6) | (3 << 11)) << 32);   /* HW_ID, XCC_ID[3:0] */ \
+        } } while (0)
+#else
+#define QL_TL_DECL() do { } while (0)
+#define QL_TL(i) do { } while (0)
+#define QL_TL_DEP(x) do { } while (0)
+#define QL_TL_LANDED() do { } while (0)
+#define QL_TL_WRITE() do { } while (0)
+#endif
+
 // The kernel body is a device function taking its block coordinates as arguments, so that ONE launch can run two
 // projections (w4_mlp_pair_kernel below: blocks [0, nA) = the first, the rest = the second, chained through counters).
 // CHAIN: 0 none; 1 = this projection's outputs feed a chained consumer in the same launch (outputs stored, block arrives on
@@ -184,7 +213,16 @@ struct ChainArgs {
 constexpr int kChainSlots = 64;
 constexpr int kChainWords = 16 * (kChainSlots + 3);
 
-template <typename T, int MB, int ACH, int KS, bool STRICT, int VAR = 0, int PRO = PRO_NONE, int CHAIN = 0>   // ACH: 16-byte A chunks staged per thread; 0 = A from global
+// ONE_TILE (one row, every wave's K slice <= 64 groups - the decode shapes up to K = 8192, the headline among them): no tile loop and no
+// second register tile; the scale is requested in front of the weight words, the activation reads and the activation-only sums (`corr`)
+// are issued before anything waits on a weight, and each column's unpack + dots waits for its own weight word only.
+// CW (ONE_TILE only): columns of its quad a wave owns, 4 or 2.  With 2, KS * 2 waves serve a quad: twice the waves, each with half the
+// work that sits behind its last weight byte; the quad's sums meet in LDS and ONE wave runs today's epilogue on all four of them.
+// Per column nothing changes - same loads, same e / o chains, same fma, same wave_sum, same K-slice add order, same rounding.
+// With a bias or a residual the epilogue operands are requested behind the weights inside a kernel-uniform branch, and the compiler
+// counts for the path without them: there the first column's wait already covers the last weight word (the hoisted activation work
+// stays in front of it; the per-column waits are progressive for the plain forward and the fused entries without bias only).
+template <typename T, int MB, int ACH, int KS, bool STRICT, int VAR = 0, int PRO = PRO_NONE, int CHAIN = 0, bool ONE_TILE = false, int CW = 4>   // ACH: 16-byte A chunks staged per thread; 0 = A from global
 __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, const u32x4* __restrict__ Wt,
                                                        const T* __restrict__ Sp, const void* pro_delta,
                                                        const void* pro_ln_weight, int N, int K, int M, int lda32,
@@ -205,11 +243,18 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
     constexpr bool A_LDS = ACH > 0;
     typedef Splice<T> SP;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int QW = 4 / KS;                 // column quads per block
+    static_assert(CW == 4 || (CW == 2 && ONE_TILE && KS <= 2), "a quad's waves share a block");
+    static_assert(!ONE_TILE || (MB == 1 && A_LDS && VAR == 0 && CHAIN == 0), "the one-tile path is the one-row LDS-staged product kernel");
+    constexpr int WPQ = KS * (4 / CW);         // waves per column quad
+    constexpr int QW = 4 / WPQ;                // column quads per block
+    constexpr int NC = ONE_TILE ? CW : 4;      // columns per wave
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     QL_SPAN_START();
+    QL_TL_DECL();
+    QL_TL(0);
     const int ks = wave % KS;
-    const int t_raw = bx * QW + wave / KS;
+    const int cw0 = CW == 4 ? 0 : (wave % WPQ) / KS * CW;   // first of this wave's columns within its quad
+    const int t_raw = bx * QW + wave / WPQ;
     const bool wave_active = t_raw * 4 < N;
     const int t = wave_active ? t_raw : 0;     // inactive waves shadow quad 0 (they must reach the barriers)
     const int m0 = by * MB;
@@ -273,9 +318,19 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
     };
 
     // (2) two weight tiles in flight before anything waits
-    PackedTile16<MB, A_LDS> t0 = load_tile(0);
-    PackedTile16<MB, A_LDS> t1;
-    if (iters > 1) t1 = load_tile(1);          // wave-uniform branch around the whole tile
+    PackedTile16<MB, A_LDS> t0, t1;
+    if constexpr (ONE_TILE) {
+        // the one tile: scales first (needed by every column, so never the last arrival), then this wave's NC weight words
+        const int g = g_begin + lane;
+        const int gc = g < g_end ? g : G - 1;
+        if constexpr (CW == 4) t0.s = *reinterpret_cast<const u32x2*>(sbase + (int64_t)gc * 4);
+        else t0.s = u32x2{*reinterpret_cast<const u32*>(sbase + (int64_t)gc * 4 + cw0), 0u};
+#pragma unroll
+        for (int c = 0; c < NC; ++c) t0.w[c] = QL_GEMV_W_LOAD(wbase + (int64_t)(cw0 + c) * G + gc);
+    } else {
+        t0 = load_tile(0);
+        if (iters > 1) t1 = load_tile(1);      // wave-uniform branch around the whole tile
+    }
 
     // Epilogue operands of this wave's column quad (bias, residual) requested behind the weight tiles: fetched at
     // the end they are a global round trip in the tail of every wave (the residual epilogue measured no gain that way);
@@ -385,6 +440,7 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
         }
         __syncthreads();
     }
+    QL_TL(1);
 
     float acc[MB][4];
 #pragma unroll
@@ -395,6 +451,7 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
     auto compute_tile = [&](const PackedTile16<MB, A_LDS>& tl, int it) {
         const int g = g_begin + it * 64 + lane;
         const int gc = g < g_end ? g : G - 1;
+        if constexpr (!ONE_TILE) QL_TL_LANDED();
         u32 av[MB][16];                                       // av[m][i] = (a[2i], a[2i+1]) of this lane's group
 #pragma unroll
         for (int m = 0; m < MB; ++m)
@@ -412,6 +469,32 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
                 av[m][4 * j + 2] = x[2];
                 av[m][4 * j + 3] = x[3];
             }
+        // one tile: everything that needs the activations alone goes first and stays there - the LDS reads and, in the default
+        // arithmetic, the group's activation sums - so that it runs under the weights' flight instead of behind their last byte
+        float corr_early = 0.f;
+        if constexpr (ONE_TILE) {
+            if constexpr (!STRICT) {
+                float e = 0.f, o = 0.f;
+#pragma unroll
+                for (int i = 0; i < 16; i += 2) {
+                    e = SP::dot(SP::kOnes, av[0][i], e);
+                    o = SP::dot(SP::kOnes, av[0][i + 1], o);
+                }
+                corr_early = SP::offset(e, o);
+                // kept a product of its own: seen through, bf16's 136 (e + o) is contracted into the subtraction below (one fma, one
+                // rounding less), which the tile loop - four columns sharing the product - does not do; the results must stay its bits.
+                // Both sides of that are this compiler's choices: a toolchain change can move either kernel, and
+                // tests/test_gemv_onetile_gpu.py (bit for bit against QLINEAR_DISPATCH=noonetile) is what notices.
+                asm volatile("" : "+v"(corr_early));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        auto column_done = [&](int c) {                       // one tile: column c + 1 waits for its own weight word, not before
+            if constexpr (ONE_TILE) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (c == NC - 2) QL_TL_LANDED();
+            }
+        };
         const u32x2 sv = g < g_end ? tl.s : u32x2{0u, 0u};    // out-of-range lanes contribute 0
         if constexpr (VAR == 1 || VAR == 5 || VAR == 6 || VAR == 7) {
 #pragma unroll
@@ -432,7 +515,7 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
             const float sc[4] = {SP::lo(sv[0]), SP::hi(sv[0]), SP::lo(sv[1]), SP::hi(sv[1])};
             const float m8[4] = {-8.0f * sc[0], -8.0f * sc[1], -8.0f * sc[2], -8.0f * sc[3]};
 #pragma unroll
-            for (int c = 0; c < 4; ++c)
+            for (int c = 0; c < NC; ++c) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const u32 w = tl.w[c][j];
@@ -447,6 +530,8 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
                         for (int m = 0; m < MB; ++m) acc[m][c] = SP::dot(pr, av[m][4 * j + i], acc[m][c]);
                     }
                 }
+                column_done(c);
+            }
         } else if constexpr (STRICT) {
             const h2 k1032 = {(f16)1032.0f, (f16)1032.0f};
             const h2 kInv16 = {(f16)0.0625f, (f16)0.0625f};
@@ -456,7 +541,7 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
             const h2 s2[4] = {as_h2((sv[0] & 0xFFFFu) | (sv[0] << 16)), as_h2((sv[0] >> 16) | (sv[0] & 0xFFFF0000u)),
                               as_h2((sv[1] & 0xFFFFu) | (sv[1] << 16)), as_h2((sv[1] >> 16) | (sv[1] & 0xFFFF0000u))};
 #pragma unroll
-            for (int c = 0; c < 4; ++c)
+            for (int c = 0; c < NC; ++c) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const u32 w = tl.w[c][j], w8 = w >> 8;
@@ -475,10 +560,16 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
                         acc[m][c] = v;
                     }
                 }
+                column_done(c);
+            }
         } else {
             float corr[MB];                                   // offset * sum of this group's activations
 #pragma unroll
             for (int m = 0; m < MB; ++m) {
+                if constexpr (ONE_TILE) {
+                    corr[m] = corr_early;
+                    continue;
+                }
                 float e = 0.f, o = 0.f;
 #pragma unroll
                 for (int i = 0; i < 16; i += 2) {
@@ -489,7 +580,7 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
             }
             const float sc[4] = {SP::lo(sv[0]), SP::hi(sv[0]), SP::lo(sv[1]), SP::hi(sv[1])};
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
+            for (int c = 0; c < NC; ++c) {
                 float e[MB], o[MB];                           // two independent dot chains per row
 #pragma unroll
                 for (int m = 0; m < MB; ++m) e[m] = o[m] = 0.f;
@@ -511,6 +602,7 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
                 }
 #pragma unroll
                 for (int m = 0; m < MB; ++m) acc[m][c] = __builtin_fmaf(sc[c], SP::combine(e[m], o[m]) - corr[m], acc[m][c]);
+                column_done(c);
             }
         }
     };
@@ -521,6 +613,9 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
     // under `if (more tiles)` leaves hipcc unable to count the loads issued after a given one (it then waits
     // vmcnt(0), i.e. for the tile it just issued), and a dummy load past the end keeps the wave alive until
     // it returns (measured +15 %).  The last round is peeled instead.
+    if constexpr (ONE_TILE) {
+        compute_tile(t0, 0);                   // straight line; lanes past the slice's end are masked as in the tile loop
+    } else {
     const int full = iters >> 1;
     for (int r = 0; r + 1 < full; ++r) {
         compute_tile(t0, 2 * r);
@@ -534,13 +629,37 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
         compute_tile(t1, 2 * full - 1);
     }
     if (iters & 1) compute_tile(t0, iters - 1);
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) QL_TL_DEP(acc[0][c]);
+    QL_TL(3);
 
 #pragma unroll
     for (int m = 0; m < MB; ++m)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) acc[m][c] = wave_sum(acc[m][c]);
+        for (int c = 0; c < NC; ++c) acc[m][c] = wave_sum(acc[m][c]);
+#pragma unroll
+    for (int c = 0; c < NC; ++c) QL_TL_DEP(acc[0][c]);
+    QL_TL(4);
 
-    if constexpr (KS > 1) {
+    if constexpr (CW < 4) {
+        // the quad's waves (KS slices x 4 / CW column groups) leave their sums in LDS; the quad's first wave collects all four
+        // columns, slice 0 first and its partners added in slice order - the order below - and runs the epilogue
+        float* red = reinterpret_cast<float*>(smem + (((size_t)K * sizeof(T) + 15) & ~(size_t)15));
+        if (lane == 0) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) red[(wave / WPQ * KS + ks) * 4 + cw0 + c] = acc[0][c];
+        }
+        __syncthreads();
+        if (wave % WPQ == 0 && lane == 0) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                acc[0][c] = red[(wave / WPQ * KS) * 4 + c];
+#pragma unroll
+                for (int p = 1; p < KS; ++p) acc[0][c] += red[(wave / WPQ * KS + p) * 4 + c];
+            }
+        }
+    } else if constexpr (KS > 1) {
         // combine the K slices of a quad: slice 0 of each quad adds its partners' sums
         float* red = reinterpret_cast<float*>(smem + (A_LDS ? (((size_t)MB * K * sizeof(T) + 15) & ~(size_t)15) : 0));
         if (lane == 0) {
@@ -561,8 +680,9 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
     }
 
     QL_SPAN_END();
+    QL_TL(5);
     auto epilogue = [&] {
-    if (wave_active && ks == 0 && lane == 0) {
+    if (wave_active && ks == 0 && cw0 == 0 && lane == 0) {
         float bq[4] = {0.f, 0.f, 0.f, 0.f}, rq[4] = {0.f, 0.f, 0.f, 0.f};
         if (quad_early) {
             unpack2<T>(bias_q[0], bq[0], bq[1]);
@@ -621,6 +741,8 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
     }
     };
     epilogue();
+    QL_TL(6);
+    QL_TL_WRITE();
     if constexpr (CHAIN == 1) {
         // outputs -> visible to the consumer blocks of this launch (cdna_hip_programming.md Guideline 16, R1): the payload went
         // out write-through, every storing wave drains its stores, block barrier, one lane arrives
@@ -648,6 +770,18 @@ __global__ __launch_bounds__(256, (MB == 1 ? QL_GEMV_MIN_WAVES : 1)) void w4_pac
                                                                 const T* __restrict__ resid = nullptr) {
     w4_packed_gemv_16_body<T, MB, ACH, KS, STRICT, VAR, PRO>(A, Wt, Sp, pro_delta, pro_ln_weight, N, K, M, lda32, bias, C, ldc, pro_hout,
                                                               pro_eps, pro_gate, resid, (int)blockIdx.x, (int)blockIdx.y);
+}
+
+// one row, one 64-group tile per wave (body: ONE_TILE)
+template <typename T, int ACH, int KS, bool STRICT, int PRO, int CW>
+__global__ __launch_bounds__(256, QL_GEMV_MIN_WAVES) void w4_packed_gemv_16_onetile_kernel(const T* __restrict__ A, const u32x4* __restrict__ Wt,
+                                                                const T* __restrict__ Sp, const void* pro_delta,
+                                                                const void* pro_ln_weight, int N, int K, int M, int lda32,
+                                                                const T* __restrict__ bias, T* __restrict__ C, int64_t ldc,
+                                                                void* pro_hout, float pro_eps, int pro_gate,
+                                                                const T* __restrict__ resid = nullptr) {
+    w4_packed_gemv_16_body<T, 1, ACH, KS, STRICT, 0, PRO, 0, true, CW>(A, Wt, Sp, pro_delta, pro_ln_weight, N, K, M, lda32, bias, C, ldc,
+                                                                       pro_hout, pro_eps, pro_gate, resid, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -824,6 +958,35 @@ static int choose_ksplit(int64_t quads, int64_t G, int mb = 1) {
 
 int w4_gemv_ksplit(int64_t quads, int64_t G) { return choose_ksplit(quads, G); }
 
+// The one-tile kernel serves one row of a 16-bit dtype when every wave's K slice is one 64-group tile (K <= 8192 at 4 slices).
+// QLINEAR_DISPATCH=noonetile: the tile-loop kernel instead (bit-equal).
+static std::atomic<uint64_t> g_onetile_launches{0};
+uint64_t w4_gemv_onetile_launches() { return g_onetile_launches.load(std::memory_order_relaxed); }
+static bool one_tile_serves(int64_t G, int ks) { return !(dispatch_flags() & QL_D_NOONETILE) && G >= ks && (G + ks - 1) / ks <= 64; }
+// Columns per wave.  Plain / residual forward: 2 where a quad's waves fit one block (profiles/gemv_onetile_ab.txt).  The fused entries
+// redo their prologue in every block, and twice the blocks is what cost w_in 4.3 % before (profiles/r06_gemv_ksplit_bound_ab.txt): 4.
+static int one_tile_cw(int ks, bool pro) {
+    const int cw = pro ? QL_TUNE("QLINEAR_ONETILE_CW_PRO", 4) : QL_TUNE("QLINEAR_ONETILE_CW", 2);
+    return ks <= 2 && cw == 2 ? 2 : 4;
+}
+
+template <typename T, int ACH, int KS, bool STRICT, int PRO, int CW>
+static int launch_16_onetile(const PackedArgs& p, const Prologue& pro) {
+    const int64_t G = p.K / 32, Npad = (p.N + 3) & ~(int64_t)3;
+    const u32x4* Wt = (const u32x4*)p.packed;
+    const T* Sp = (const T*)((const char*)p.packed + Npad * G * 16);
+    const int quads = (int)(Npad / 4);
+    constexpr int QW = 4 / (KS * (4 / CW));
+    dim3 grid((unsigned)((quads + QW - 1) / QW), 1);
+    // the staged row, 16 floats for the quad's sums, 4 for the norm prologue's
+    const size_t lds = (((size_t)p.K * sizeof(T) + 15) & ~(size_t)15) + 4 * 4 * sizeof(float) + 4 * sizeof(float);
+    w4_packed_gemv_16_onetile_kernel<T, ACH, KS, STRICT, PRO, CW><<<grid, 256, lds, p.st>>>(
+        (const T*)p.A, Wt, Sp, pro.delta, pro.ln_weight, p.N, p.K, 1, (int)p.lda, (const T*)p.bias, (T*)p.C, p.ldc, pro.hout, pro.eps,
+        pro.gate_epilogue, (const T*)p.resid);
+    g_onetile_launches.fetch_add(1, std::memory_order_relaxed);
+    return finish_launch(QL_K_W4_GEMV);
+}
+
 template <typename T, int MB, int ACH, int KS, bool STRICT>
 static int launch_16(const PackedArgs& p) {
     const int64_t G = p.K / 32, Npad = (p.N + 3) & ~(int64_t)3;
@@ -834,6 +997,17 @@ static int launch_16(const PackedArgs& p) {
     dim3 grid((unsigned)((quads + QW - 1) / QW), (unsigned)((p.M + MB - 1) / MB));
     const size_t lds = (ACH > 0 ? (((size_t)MB * p.K * sizeof(T) + 15) & ~(size_t)15) : 0) +
                        (KS > 1 ? (size_t)4 * MB * 4 * sizeof(float) : 0);
+    if constexpr (MB == 1 && (ACH == 2 || ACH == 4)) {         // (one tile per wave: K <= 8192, at most 4 staged chunks per thread)
+#ifdef QL_DEV_VARIANTS
+        if (dev_variant() == 0)
+#endif
+        if (one_tile_serves(G, KS)) {
+            const Prologue none{nullptr, nullptr, nullptr, 0.f, 0};
+            if constexpr (KS <= 2)
+                if (one_tile_cw(KS, false) == 2) return launch_16_onetile<T, ACH, KS, STRICT, PRO_NONE, 2>(p, none);
+            return launch_16_onetile<T, ACH, KS, STRICT, PRO_NONE, 4>(p, none);
+        }
+    }
 #ifdef QL_DEV_VARIANTS
     if constexpr (MB == 1 && !STRICT) {
         if (dev_variant() == 1) {
@@ -920,6 +1094,15 @@ static int launch_16_pro(const PackedArgs& p, const Prologue& pro) {
     constexpr int QW = 4 / KS;
     dim3 grid((unsigned)((quads + QW - 1) / QW), 1);
     const size_t lds = (((size_t)p.K * sizeof(T) + 15) & ~(size_t)15) + 4 * 4 * sizeof(float) + 4 * sizeof(float);
+    if constexpr (ACH == 2 || ACH == 4) {
+        if (one_tile_serves(G, KS)) {
+#ifdef QL_DEV_TUNING                                           // the two-column geometry of the fused entries: measured, not shipped
+            if constexpr (KS <= 2)
+                if (one_tile_cw(KS, true) == 2) return launch_16_onetile<T, ACH, KS, STRICT, PRO, 2>(p, pro);
+#endif
+            return launch_16_onetile<T, ACH, KS, STRICT, PRO, 4>(p, pro);
+        }
+    }
     w4_packed_gemv_16_kernel<T, 1, ACH, KS, STRICT, 0, PRO><<<grid, 256, lds, p.st>>>(
         (const T*)p.A, Wt, Sp, pro.delta, pro.ln_weight, p.N, p.K, 1, (int)p.lda, (const T*)p.bias, (T*)p.C, p.ldc, pro.hout, pro.eps,
         pro.gate_epilogue);
@@ -1202,5 +1385,26 @@ extern "C" int qlinear_span_read(unsigned long long* first_start, unsigned long 
     *last_end = hi;
     *waves = n;
     return rc;
+}
+#endif
+
+#ifdef QL_TIMELINE_PROBE
+// developer entry points of the timeline build (tools/gemv_onetile_timeline.py)
+extern "C" int qlinear_timeline_reset_async(void* stream) {
+    void* p = nullptr;
+    const int rc = (int)hipGetSymbolAddress(&p, HIP_SYMBOL(ql::ql_tl_slots));
+    if (rc) return rc;
+    return (int)hipMemsetD32Async((hipDeviceptr_t)p, 0u, 2 * ql::kTlWords * ql::kTlWaves, (hipStream_t)stream);
+}
+extern "C" int qlinear_timeline_clock_khz(void) {
+    int dev = 0, khz = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess) return 0;
+    return khz;
+}
+extern "C" int qlinear_timeline_slots(void) { return ql::kTlWaves; }
+// host-synchronous: the raw slots (8 words per wave: seven stations, then HW_ID | XCC_ID << 32); an unwritten slot is all zero
+extern "C" int qlinear_timeline_read(unsigned long long* host) {
+    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(ql::ql_tl_slots), sizeof(unsigned long long) * ql::kTlWords * ql::kTlWaves);
 }
 #endif

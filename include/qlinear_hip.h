@@ -52,7 +52,8 @@ extern "C" {
  * (qlinear_greedy_advance, qlinear_top_p_sample, qlinear_batch_sample_advance) are unchanged, they read the adjusted logits.
  * Still 3: qlinear_gptq_block added - purely additive.
  * Still 3: qlinear_step_logprobs (and the constant QL_TOP_LOGPROBS_MAX) added - purely additive; qlinear_token_logprob and the
- * selection entry points are unchanged. */
+ * selection entry points are unchanged.
+ * Still 3: qlinear_w4g32_onetile_launches and the QLINEAR_DISPATCH family `noonetile` (flag bit 8) added - purely additive. */
 #define QLINEAR_ABI_VERSION 3
 
 /* activation dtypes */
@@ -122,17 +123,21 @@ uint64_t qlinear_launch_count(void);
 #define QL_K_ACT_QUANT 18
 #define QL_K_W4_ROWS16 19       /* w4_rows16.hip: 3..16 rows on v_mfma_f32_16x16x32, part 1, one launch */
 uint64_t qlinear_last_dispatch(void);
+/* Launches of the one-tile one-row int4g32 GEMV (QL_K_W4_GEMV's straight-line kernel) since the library was loaded: which of the two
+ * GEMV kernels served a call is not visible in its family code. */
+uint64_t qlinear_w4g32_onetile_launches(void);
 void qlinear_dispatch_reset(void);
 void qlinear_dispatch_reload(void);   /* parse QLINEAR_DISPATCH again (it is read once, at the first dispatch decision) */
 /* The parsed QLINEAR_DISPATCH switches as the library holds them (bit 0 no256, 1 nopeel, 2 nofewrow, 3 norows4, 4 nogroupattn,
- * 5 nohalf, 6 nof32mfma, 7 norows16): a host that sizes a workspace or picks an entry point by one of them asks here instead of parsing the variable again. */
+ * 5 nohalf, 6 nof32mfma, 7 norows16, 8 noonetile): a host that sizes a workspace or picks an entry point by one of them asks here instead of parsing the variable again. */
 unsigned qlinear_dispatch_flags(void);
 
 /* Environment variables read by THIS library (chatglm_q_amd/csrc/tune.h): exactly one,
  *   QLINEAR_DISPATCH = comma list of kernel families the dispatch must not use: no256, nopeel, nofewrow, norows4, nogroupattn,
  *   nohalf (the half-tile last round inside the int4g32 256-tile GEMM's launch: whole tiles only, the older peel where it applies),
  *   nof32mfma (the fp32 matrix-instruction kernel that serves fp32 activations from 128 rows on: the VALU kernels instead),
- *   norows16 (the one-launch 3..16-row kernel on part 1: the few-row kernel on part 2 instead)
+ *   norows16 (the one-launch 3..16-row kernel on part 1: the few-row kernel on part 2 instead),
+ *   noonetile (the straight-line one-row int4g32 GEMV that serves K slices of one 64-group tile: the tile-loop kernel instead, bit-equal)
  * (every family has a slower fallback computing the same function; for A/B measurements and triage).  The host package reads
  * QLINEAR_LIB_PATH (another build of this library) and QLINEAR_STRICT (0 / 1 / auto: the per-weight rounding policy, see
  * QL_FLAG_STRICT_ROUNDING) - chatglm_q_amd/_lib.py.  Every other tuning value is a compile-time constant with its measurement
