@@ -222,7 +222,17 @@ constexpr int kChainWords = 16 * (kChainSlots + 3);
 // With a bias or a residual the epilogue operands are requested behind the weights inside a kernel-uniform branch, and the compiler
 // counts for the path without them: there the first column's wait already covers the last weight word (the hoisted activation work
 // stays in front of it; the per-column waits are progressive for the plain forward and the fused entries without bias only).
-template <typename T, int MB, int ACH, int KS, bool STRICT, int VAR = 0, int PRO = PRO_NONE, int CHAIN = 0, bool ONE_TILE = false, int CW = 4>   // ACH: 16-byte A chunks staged per thread; 0 = A from global
+// LEAN (ONE_TILE, PRO_NONE only): the body knows M == 1 and blockIdx.y == 0 - no row clamp, no lda multiply - and addresses the x row,
+// the scales and the weight words by unsigned 32-bit byte offsets against the scalar bases (the launcher checks that Npad * G * 16 fits
+// 31 bits and takes the other body when it does not); order of the requests unchanged: x row, scale, weight words, late operands.
+// TICKET (CW == 2 only): the quad's sums meet in LDS without the barrier hand-over.  Lane 0 of every wave issues the write of its sums
+// and a returning add of 1 on its quad's ticket word back to back, waits for both, and then reads the quad's whole `red` region (the
+// two-hop form: the reads are issued only when the ticket is back, so nothing rests on how the LDS unit orders the operations of
+// different waves beyond serialising the atomics on a word).  The wave whose ticket reads WPQ - 1 arrived last: every partner's write
+// was counted ahead of that partner's ticket, so it holds all sums, adds them in the order below and runs the epilogue.  The others
+// are done.  Nothing waits for another wave.  The ticket words are zeroed by thread 0 in front of the staging barrier.
+template <typename T, int MB, int ACH, int KS, bool STRICT, int VAR = 0, int PRO = PRO_NONE, int CHAIN = 0, bool ONE_TILE = false, int CW = 4,
+          bool LEAN = false, bool TICKET = false>   // ACH: 16-byte A chunks staged per thread; 0 = A from global
 __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, const u32x4* __restrict__ Wt,
                                                        const T* __restrict__ Sp, const void* pro_delta,
                                                        const void* pro_ln_weight, int N, int K, int M, int lda32,
@@ -245,6 +255,8 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(CW == 4 || (CW == 2 && ONE_TILE && KS <= 2), "a quad's waves share a block");
     static_assert(!ONE_TILE || (MB == 1 && A_LDS && VAR == 0 && CHAIN == 0), "the one-tile path is the one-row LDS-staged product kernel");
+    static_assert(!LEAN || (ONE_TILE && PRO == PRO_NONE), "the lean entry is the plain / residual one-tile forward's");
+    static_assert(!TICKET || (ONE_TILE && CW == 2), "tickets are drawn by the two-column waves of a quad");
     constexpr int WPQ = KS * (4 / CW);         // waves per column quad
     constexpr int QW = 4 / WPQ;                // column quads per block
     constexpr int NC = ONE_TILE ? CW : 4;      // columns per wave
@@ -273,7 +285,7 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
 
     const T* arow[MB];
 #pragma unroll
-    for (int m = 0; m < MB; ++m) arow[m] = A + (int64_t)((m0 + m < M) ? (m0 + m) : (M - 1)) * lda;
+    for (int m = 0; m < MB; ++m) arow[m] = LEAN ? A : A + (int64_t)((m0 + m < M) ? (m0 + m) : (M - 1)) * lda;
 
     // (1) activation staging loads first: oldest in the VM queue
     u32x4 areg[A_LDS ? ACH : 1];
@@ -287,7 +299,8 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
                 // around it and drain the queue (vmcnt(0)) per element
                 const int c = min(tid + i * 256, MB * cpr - 1);
                 const int m = MB == 1 ? 0 : c / cpr, cc = c - m * cpr;
-                areg[i] = *reinterpret_cast<const u32x4*>(arow[m] + cc * 8);
+                if constexpr (LEAN) areg[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(A) + (u32)c * 16u);
+                else areg[i] = *reinterpret_cast<const u32x4*>(arow[m] + cc * 8);
                 if constexpr (PRO == PRO_SILU) xreg[i] = *reinterpret_cast<const u32x4*>(arow[0] + K + cc * 8);
                 if constexpr (kNorm) xreg[i] = *reinterpret_cast<const u32x4*>((const T*)pro.ln_weight + cc * 8);
                 if constexpr (PRO == PRO_ADDNORM)
@@ -323,10 +336,21 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
         // the one tile: scales first (needed by every column, so never the last arrival), then this wave's NC weight words
         const int g = g_begin + lane;
         const int gc = g < g_end ? g : G - 1;
-        if constexpr (CW == 4) t0.s = *reinterpret_cast<const u32x2*>(sbase + (int64_t)gc * 4);
-        else t0.s = u32x2{*reinterpret_cast<const u32*>(sbase + (int64_t)gc * 4 + cw0), 0u};
+        if constexpr (LEAN) {
+            const u32 soff = ((u32)(t * G + gc) * 4u + (u32)cw0) * (u32)sizeof(T);
+            const u32 woff = ((u32)(t * 4 + cw0) * (u32)G + (u32)gc) * 16u;
+            const char* sb = reinterpret_cast<const char*>(Sp);
+            const char* wb = reinterpret_cast<const char*>(Wt);
+            if constexpr (CW == 4) t0.s = *reinterpret_cast<const u32x2*>(sb + soff);
+            else t0.s = u32x2{*reinterpret_cast<const u32*>(sb + soff), 0u};
 #pragma unroll
-        for (int c = 0; c < NC; ++c) t0.w[c] = QL_GEMV_W_LOAD(wbase + (int64_t)(cw0 + c) * G + gc);
+            for (int c = 0; c < NC; ++c) t0.w[c] = QL_GEMV_W_LOAD(reinterpret_cast<const u32x4*>(wb + (woff + (u32)c * ((u32)G * 16u))));
+        } else {
+            if constexpr (CW == 4) t0.s = *reinterpret_cast<const u32x2*>(sbase + (int64_t)gc * 4);
+            else t0.s = u32x2{*reinterpret_cast<const u32*>(sbase + (int64_t)gc * 4 + cw0), 0u};
+#pragma unroll
+            for (int c = 0; c < NC; ++c) t0.w[c] = QL_GEMV_W_LOAD(wbase + (int64_t)(cw0 + c) * G + gc);
+        }
     } else {
         t0 = load_tile(0);
         if (iters > 1) t1 = load_tile(1);      // wave-uniform branch around the whole tile
@@ -430,6 +454,13 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
         for (int i = 0; i < ACH; ++i) asm volatile("" ::"v"(areg[i][0]));   // keep the loads
     }
     if constexpr (A_LDS && VAR != 4 && VAR != 5 && VAR != 7) {
+        if constexpr (TICKET) {                // arrival tickets of the block's quads: behind the quad sums and the norm prologue's floats
+            u32* ticket = reinterpret_cast<u32*>(smem + (((size_t)K * sizeof(T) + 15) & ~(size_t)15) + (4 * 4 + 4) * sizeof(float));
+            if (tid == 0) {
+#pragma unroll
+                for (int q = 0; q < QW; ++q) ticket[q] = 0u;
+            }
+        }
 #pragma unroll
         for (int i = 0; i < ACH; ++i) {
             const int c = tid + i * 256;
@@ -642,7 +673,36 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
     for (int c = 0; c < NC; ++c) QL_TL_DEP(acc[0][c]);
     QL_TL(4);
 
-    if constexpr (CW < 4) {
+    bool owner = ks == 0 && cw0 == 0;          // the wave of a quad that runs the epilogue
+    if constexpr (TICKET) {
+        static_assert(!TICKET || (NC == 2 && (KS == 1 || KS == 2)), "one 8-byte write, one or two 16-byte reads");
+        typedef __attribute__((address_space(3))) char lds_char;
+        const u32 red0 = (u32)(uintptr_t)(lds_char*)smem + (u32)(((size_t)K * sizeof(T) + 15) & ~(size_t)15);
+        const int q = wave / WPQ;
+        owner = false;
+        if (lane == 0) {
+            const u32 wa = red0 + (u32)((q * KS + ks) * 4 + cw0) * 4u, ra = red0 + (u32)(q * KS) * 16u, ta = red0 + 80u + (u32)q * 4u;
+            const u32x2 mine = {f32_as_u32(acc[0][0]), f32_as_u32(acc[0][1])};
+            u32x4 r0, r1 = {0u, 0u, 0u, 0u};
+            u32 drawn;
+            // two hops: the write and the ticket in one statement with a wait behind them, then the reads.  A wave's write is counted
+            // ahead of its ticket (lgkmcnt retires a wave's LDS operations in the order issued), so when this wave's ticket has come back
+            // as the last one, every partner's write has landed before the reads below are issued
+            asm volatile("ds_write_b64 %1, %2\n\tds_add_rtn_u32 %0, %3, %4\n\ts_waitcnt lgkmcnt(0)"
+                         : "=&v"(drawn) : "v"(wa), "v"(mine), "v"(ta), "v"(1u) : "memory");
+            if constexpr (KS == 2)
+                asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16\n\ts_waitcnt lgkmcnt(0)"
+                             : "=&v"(r0), "=&v"(r1) : "v"(ra) : "memory");
+            else
+                asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(r0) : "v"(ra) : "memory");
+            owner = drawn == (u32)(WPQ - 1);   // arrived last: the reads above hold every partner's sums (the others' are not used)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                acc[0][c] = u32_as_f32(r0[c]);
+                if constexpr (KS == 2) acc[0][c] += u32_as_f32(r1[c]);
+            }
+        }
+    } else if constexpr (CW < 4) {
         // the quad's waves (KS slices x 4 / CW column groups) leave their sums in LDS; the quad's first wave collects all four
         // columns, slice 0 first and its partners added in slice order - the order below - and runs the epilogue
         float* red = reinterpret_cast<float*>(smem + (((size_t)K * sizeof(T) + 15) & ~(size_t)15));
@@ -682,7 +742,7 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
     QL_SPAN_END();
     QL_TL(5);
     auto epilogue = [&] {
-    if (wave_active && ks == 0 && cw0 == 0 && lane == 0) {
+    if (wave_active && owner && lane == 0) {
         float bq[4] = {0.f, 0.f, 0.f, 0.f}, rq[4] = {0.f, 0.f, 0.f, 0.f};
         if (quad_early) {
             unpack2<T>(bias_q[0], bq[0], bq[1]);
@@ -773,15 +833,26 @@ __global__ __launch_bounds__(256, (MB == 1 ? QL_GEMV_MIN_WAVES : 1)) void w4_pac
 }
 
 // one row, one 64-group tile per wave (body: ONE_TILE)
-template <typename T, int ACH, int KS, bool STRICT, int PRO, int CW>
+template <typename T, int ACH, int KS, bool STRICT, int PRO, int CW, bool TICKET = false>
 __global__ __launch_bounds__(256, QL_GEMV_MIN_WAVES) void w4_packed_gemv_16_onetile_kernel(const T* __restrict__ A, const u32x4* __restrict__ Wt,
                                                                 const T* __restrict__ Sp, const void* pro_delta,
                                                                 const void* pro_ln_weight, int N, int K, int M, int lda32,
                                                                 const T* __restrict__ bias, T* __restrict__ C, int64_t ldc,
                                                                 void* pro_hout, float pro_eps, int pro_gate,
                                                                 const T* __restrict__ resid = nullptr) {
-    w4_packed_gemv_16_body<T, 1, ACH, KS, STRICT, 0, PRO, 0, true, CW>(A, Wt, Sp, pro_delta, pro_ln_weight, N, K, M, lda32, bias, C, ldc,
-                                                                       pro_hout, pro_eps, pro_gate, resid, (int)blockIdx.x, (int)blockIdx.y);
+    w4_packed_gemv_16_body<T, 1, ACH, KS, STRICT, 0, PRO, 0, true, CW, false, TICKET>(A, Wt, Sp, pro_delta, pro_ln_weight, N, K, M, lda32, bias, C,
+                                                                                      ldc, pro_hout, pro_eps, pro_gate, resid, (int)blockIdx.x,
+                                                                                      (int)blockIdx.y);
+}
+
+// ... plain / residual forward with the lean entry (body: LEAN).  One row, no prologue: eight arguments, 14 dwords - every one of them,
+// the late operands' pointers included, is preloaded into SGPRs at wave launch, so the kernel issues no scalar load at all.
+template <typename T, int ACH, int KS, bool STRICT, int CW, bool TICKET>
+__global__ __launch_bounds__(256, QL_GEMV_MIN_WAVES) void w4_packed_gemv_16_onetile_lean_kernel(const T* __restrict__ A, const u32x4* __restrict__ Wt,
+                                                                const T* __restrict__ Sp, int N, int K, const T* __restrict__ bias,
+                                                                T* __restrict__ C, const T* __restrict__ resid) {
+    w4_packed_gemv_16_body<T, 1, ACH, KS, STRICT, 0, PRO_NONE, 0, true, CW, true, TICKET>(A, Wt, Sp, nullptr, nullptr, N, K, 1, 0, bias, C, 0, nullptr,
+                                                                                          0.f, 0, resid, (int)blockIdx.x, 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -970,7 +1041,20 @@ static int one_tile_cw(int ks, bool pro) {
     return ks <= 2 && cw == 2 ? 2 : 4;
 }
 
-template <typename T, int ACH, int KS, bool STRICT, int PRO, int CW>
+// Plain / residual forward (profiles/gemv_entry_exit_ab.txt): QL_ONETILE_LEAN = the lean entry wherever the packed buffer's byte offsets
+// fit 31 bits: 3.83 -> 3.77 us on the headline shape, shipped.  QL_ONETILE_TICKET = the barrier-free quad combine of the two-column
+// geometry: the combine itself shrinks (200 -> 120 ns in the timeline) and the launch gets 0.07 - 0.09 us SLOWER, with and without the
+// lean entry - measured, not shipped; the developer library keeps it behind QLINEAR_ONETILE_TICKET=1.
+#ifndef QL_ONETILE_LEAN
+#define QL_ONETILE_LEAN 1
+#endif
+#ifndef QL_ONETILE_TICKET
+#define QL_ONETILE_TICKET 0
+#endif
+static bool one_tile_lean(int64_t packed_bytes) { return QL_TUNE("QLINEAR_ONETILE_LEAN", QL_ONETILE_LEAN) != 0 && packed_bytes < ((int64_t)1 << 31); }
+static bool one_tile_ticket() { return QL_TUNE("QLINEAR_ONETILE_TICKET", QL_ONETILE_TICKET) != 0; }
+
+template <typename T, int ACH, int KS, bool STRICT, int PRO, int CW, bool LEAN = false, bool TICKET = false>
 static int launch_16_onetile(const PackedArgs& p, const Prologue& pro) {
     const int64_t G = p.K / 32, Npad = (p.N + 3) & ~(int64_t)3;
     const u32x4* Wt = (const u32x4*)p.packed;
@@ -978,13 +1062,33 @@ static int launch_16_onetile(const PackedArgs& p, const Prologue& pro) {
     const int quads = (int)(Npad / 4);
     constexpr int QW = 4 / (KS * (4 / CW));
     dim3 grid((unsigned)((quads + QW - 1) / QW), 1);
-    // the staged row, 16 floats for the quad's sums, 4 for the norm prologue's
-    const size_t lds = (((size_t)p.K * sizeof(T) + 15) & ~(size_t)15) + 4 * 4 * sizeof(float) + 4 * sizeof(float);
-    w4_packed_gemv_16_onetile_kernel<T, ACH, KS, STRICT, PRO, CW><<<grid, 256, lds, p.st>>>(
-        (const T*)p.A, Wt, Sp, pro.delta, pro.ln_weight, p.N, p.K, 1, (int)p.lda, (const T*)p.bias, (T*)p.C, p.ldc, pro.hout, pro.eps,
-        pro.gate_epilogue, (const T*)p.resid);
+    // the staged row, 16 floats for the quad's sums, 4 for the norm prologue's; with tickets one 16-byte slot for the quads' arrival tickets
+    const size_t lds = (((size_t)p.K * sizeof(T) + 15) & ~(size_t)15) + 4 * 4 * sizeof(float) + 4 * sizeof(float) + (TICKET ? 16 : 0);
+    if constexpr (LEAN)
+        w4_packed_gemv_16_onetile_lean_kernel<T, ACH, KS, STRICT, CW, TICKET><<<grid, 256, lds, p.st>>>(
+            (const T*)p.A, Wt, Sp, p.N, p.K, (const T*)p.bias, (T*)p.C, (const T*)p.resid);
+    else
+        w4_packed_gemv_16_onetile_kernel<T, ACH, KS, STRICT, PRO, CW, TICKET><<<grid, 256, lds, p.st>>>(
+            (const T*)p.A, Wt, Sp, pro.delta, pro.ln_weight, p.N, p.K, 1, (int)p.lda, (const T*)p.bias, (T*)p.C, p.ldc, pro.hout, pro.eps,
+            pro.gate_epilogue, (const T*)p.resid);
     g_onetile_launches.fetch_add(1, std::memory_order_relaxed);
     return finish_launch(QL_K_W4_GEMV);
+}
+
+// ... of the two-column geometry with one combination of the two switches.  The developer library builds all four and the environment
+// chooses; the product library builds what its two constants can reach: their combination and, for a packed buffer past 31 bits, the
+// same combine behind the body with 64-bit addresses.
+#ifdef QL_DEV_TUNING
+constexpr bool kOneTileSwitches = true;
+#else
+constexpr bool kOneTileSwitches = false;
+#endif
+template <typename T, int ACH, int KS, bool STRICT, bool LEAN, bool TICKET>
+static int launch_16_onetile_cw2(const PackedArgs& p) {
+    if constexpr (kOneTileSwitches || ((!LEAN || QL_ONETILE_LEAN != 0) && TICKET == (QL_ONETILE_TICKET != 0)))
+        return launch_16_onetile<T, ACH, KS, STRICT, PRO_NONE, 2, LEAN, TICKET>(p, Prologue{nullptr, nullptr, nullptr, 0.f, 0});
+    else
+        return QL_ERR_UNSUPPORTED;             // not reachable: one_tile_lean() / one_tile_ticket() are these constants in this build
 }
 
 template <typename T, int MB, int ACH, int KS, bool STRICT>
@@ -1004,7 +1108,11 @@ static int launch_16(const PackedArgs& p) {
         if (one_tile_serves(G, KS)) {
             const Prologue none{nullptr, nullptr, nullptr, 0.f, 0};
             if constexpr (KS <= 2)
-                if (one_tile_cw(KS, false) == 2) return launch_16_onetile<T, ACH, KS, STRICT, PRO_NONE, 2>(p, none);
+                if (one_tile_cw(KS, false) == 2) {
+                    const bool lean = one_tile_lean(Npad * G * 16), ticket = one_tile_ticket();
+                    if (lean) return ticket ? launch_16_onetile_cw2<T, ACH, KS, STRICT, true, true>(p) : launch_16_onetile_cw2<T, ACH, KS, STRICT, true, false>(p);
+                    return ticket ? launch_16_onetile_cw2<T, ACH, KS, STRICT, false, true>(p) : launch_16_onetile_cw2<T, ACH, KS, STRICT, false, false>(p);
+                }
             return launch_16_onetile<T, ACH, KS, STRICT, PRO_NONE, 4>(p, none);
         }
     }

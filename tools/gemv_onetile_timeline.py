@@ -9,7 +9,8 @@ the CUs of each CU's last-finishing wave (CU = the XCC_ID / SE_ID / SH_ID / CU_I
 
 The geometry switches are read once per process, so each configuration runs in a child process:
   tile-loop  QLINEAR_DISPATCH=noonetile (the kernel before the one-tile path)
-  cw4        one-tile path, 4 columns per wave        cw2   one-tile path, 2 columns per wave
+  cw4        one-tile path, 4 columns per wave        cw2   one-tile path, 2 columns per wave (the default dispatch: lean entry)
+  cw2-64bit  cw2 behind the entry with 64-bit addresses       cw2-ticket  cw2 with the arrival-ticket quad combine (station 5: ticket returned)
     python tools/gemv_onetile_timeline.py [--configs tile-loop,cw4,cw2] [--K 4096 --N 4096] [--reps 48]
 """
 import argparse
@@ -22,7 +23,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 LIB = os.path.join(ROOT, "chatglm_q_amd", "csrc", "libqlinear_hip_timeline.so")
 STATIONS = ["entry", "staged", "landed", "dots", "reduced", "combined", "stored"]
-CONFIGS = {"tile-loop": {"QLINEAR_DISPATCH": "noonetile"}, "cw4": {"QLINEAR_ONETILE_CW": "4"}, "cw2": {"QLINEAR_ONETILE_CW": "2"}}
+CONFIGS = {"tile-loop": {"QLINEAR_DISPATCH": "noonetile"}, "cw4": {"QLINEAR_ONETILE_CW": "4"}, "cw2": {"QLINEAR_ONETILE_CW": "2"},
+           "cw2-64bit": {"QLINEAR_ONETILE_CW": "2", "QLINEAR_ONETILE_LEAN": "0"},
+           "cw2-ticket": {"QLINEAR_ONETILE_CW": "2", "QLINEAR_ONETILE_TICKET": "1"}}
 
 
 def median(v):
