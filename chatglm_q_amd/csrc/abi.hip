@@ -827,6 +827,20 @@ int qlinear_step_logprobs(const void* logits, int64_t B, int64_t N, int64_t ldl,
     return step_logprobs(dtype, logits, B, N, ldl, tok, row_state, count, chosen, top_ids, top_lp, cap, n_top, (hipStream_t)stream);
 }
 
+int qlinear_history_constraints(void* logits, int64_t B, int64_t N, int64_t ldl, int32_t* hist, int64_t hist_ld, int32_t* hist_len,
+                                const int32_t* prompt_len, const int32_t* cfg, const int32_t* seq_tok, const int32_t* seq_len,
+                                const int32_t* seq_kind, const int32_t* seq_count, const int64_t* tok, int32_t* row_state, int32_t* live,
+                                int dtype, void* stream) {
+    if (!dtype_ok(dtype)) return QL_ERR_BAD_DTYPE;
+    if (B < 0 || B > 65535 || !fits_i32(N) || ldl < N || hist_ld < 1 || hist_ld >= ((int64_t)1 << 31)) return QL_ERR_BAD_SHAPE;
+    if (B == 0) return QL_OK;
+    if (!logits || !hist || !hist_len || !prompt_len || !cfg || !seq_tok || !seq_len || !seq_kind || !seq_count) return QL_ERR_NULL_POINTER;
+    if ((row_state == nullptr) != (live == nullptr)) return QL_ERR_NULL_POINTER;
+    if (!aligned(logits, (size_t)esize(dtype))) return QL_ERR_MISALIGNED;
+    return history_constraints(dtype, logits, B, N, ldl, hist, hist_ld, hist_len, prompt_len, cfg, seq_tok, seq_len, seq_kind, seq_count,
+                               tok, row_state, live, (hipStream_t)stream);
+}
+
 int qlinear_gptq_block(const float* W, int64_t n_rows, int64_t ldw, int64_t c0, int64_t bc, const float* hinv_block, int64_t ldh, int bits,
                        int64_t group, float* Q, float* Err, float* Loss, float* scale, int64_t lds, int dtype, void* stream) {
     if (dtype != QL_DTYPE_F32) return QL_ERR_BAD_DTYPE;

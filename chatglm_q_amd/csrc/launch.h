@@ -303,6 +303,12 @@ int logit_penalties(int dtype, void* logits, int64_t B, int64_t N, int64_t ldl, 
                     const float* bias_vals, const int32_t* bias_len, int64_t bias_cap, int32_t* state, int64_t lds, const int64_t* tok,
                     const int32_t* row_state, hipStream_t st);
 
+// history_constraints.hip: no-repeat n-grams, banned / stop sequences, minimum length in place, ordered token history kept on the device
+int history_constraints(int dtype, void* logits, int64_t B, int64_t N, int64_t ldl, int32_t* hist, int64_t hist_ld, int32_t* hist_len,
+                        const int32_t* prompt_len, const int32_t* cfg, const int32_t* seq_tok, const int32_t* seq_len,
+                        const int32_t* seq_kind, const int32_t* seq_count, const int64_t* tok, int32_t* row_state, int32_t* live,
+                        hipStream_t st);
+
 // gptq.hip: the column walk of one GPTQ block (at most 128 columns) over all weight rows in one launch; fp32
 int gptq_block(int bits, const float* W, int64_t n_rows, int64_t ldw, int64_t c0, int64_t bc, const float* H, int64_t ldh, float* Q,
                float* Err, float* Loss, float* scale, int64_t lds, hipStream_t st);

@@ -92,6 +92,14 @@ def check_logprobs(logprobs) -> Optional[int]:
     return int(logprobs)
 
 
+def matched_stop_sequence(ids, stop_sequences) -> Optional[int]:
+    """Index of the first of ``stop_sequences`` (lists of ids) that ``ids`` ends with; None when it ends with none of them."""
+    for s, q in enumerate(stop_sequences):
+        if 0 < len(q) <= len(ids) and list(ids[len(ids) - len(q):]) == list(q):
+            return s
+    return None
+
+
 class DecodeSession:
     """One sequence batch on one device: preallocated cache, eager (chunked) prefill, graph-replayed decode."""
 
@@ -143,6 +151,9 @@ class DecodeSession:
         # the record of the "+lp" steps (arm_logprobs): every generated token's log-prob and the most likely alternatives, appended
         # on the device and read once at the end.  Allocated by the first generation that asks for log-probs
         self.lp = None
+        # history constraints (arm_constraints): every row's ordered token history and its no-repeat / banned / stop / minimum-length
+        # settings in device memory, read and updated by the "+con" steps.  Allocated by the first constrained generation
+        self.con = None
         self.length = 0
         self.busy = False                                       # a generate_ids generator is running on this session
 
@@ -346,6 +357,39 @@ class DecodeSession:
         lg = logits if logits.stride(-1) == 1 else logits.contiguous()
         return fused_ops.logit_penalties(lg, self.pen, None, self.rows.row_state if rows else None)
 
+    def arm_constraints(self, prompts, no_repeat_ngram_size=0, bad_words_ids=None, stop_sequences=None, min_new_tokens=0,
+                        eos_id=None, checked=None) -> bool:
+        """Arm the history constraints for a new generation (``fused_ops.ConstraintState.arm``): ``prompts`` = the REAL prompt ids
+        of every row (no pads); ``no_repeat_ngram_size`` / ``min_new_tokens`` a scalar or one value per row, ``bad_words_ids`` /
+        ``stop_sequences`` a list of id lists (or None) or one such list per row; ``eos_id``: the id ``min_new_tokens`` holds back
+        (None: ``min_new_tokens`` arms nothing).  Returns whether anything is armed; with every control at its default nothing is
+        armed - and nothing allocated - and the generation takes the unconstrained steps.  ``checked``: the settings as
+        ``ConstraintState.check`` has already returned them for this batch (a caller that validated up front); the other arguments are
+        not looked at then."""
+        from . import fused_ops
+        B = self.batch
+        if len(prompts) != B:
+            raise ValueError(f"arm_constraints: {len(prompts)} prompts for {B} rows")
+        settings = checked if checked is not None else fused_ops.ConstraintState.check(
+            B, no_repeat_ngram_size, bad_words_ids, stop_sequences, min_new_tokens, eos_id, vocab=self.model.config.vocab_size)
+        if len(settings) != B:
+            raise ValueError(f"arm_constraints: {len(settings)} settings for {B} rows")
+        if fused_ops.ConstraintState.neutral(settings):
+            if self.con is not None:
+                self.con.active = False
+            return False
+        if self.con is None:
+            self.con = fused_ops.ConstraintState(B, self.capacity, self.device)
+        self.con.arm(prompts, settings)
+        return True
+
+    def constrain_first(self, logits: Tensor, rows: bool = False) -> Tensor:
+        """The armed history constraints applied in place to a prefill's last-position logits (nothing generated yet: nothing is
+        appended) - behind ``penalize_first``, in front of the first selection."""
+        from . import fused_ops
+        lg = logits if logits.stride(-1) == 1 else logits.contiguous()
+        return fused_ops.history_constraints(lg, self.con, None, self.rows.row_state if rows else None, self.rows.live if rows else None)
+
     def arm_logprobs(self, on: bool = True) -> bool:
         """Arm the log-prob record for a new generation (``fused_ops.StepLogprobs``: allocated on first use, one entry per cache
         position, TOP_LOGPROBS_MAX alternatives wide) - nothing recorded yet.  ``on`` False: nothing is armed or allocated and the
@@ -377,7 +421,7 @@ class DecodeSession:
         budget per row, and the stop id (None: none).  The captured "rows" step bakes the stop id in: a different one drops it."""
         self.rows.arm(params, seeds, budgets, stop_id)
         if self._rows_stop is not None and self._rows_stop != self.rows.stop_id:
-            for mode in [m for m in self._graphs if m.startswith("rows")]:       # "rows", "rows+pen", "rows+lp", "rows+pen+lp"
+            for mode in [m for m in self._graphs if m.startswith("rows")]:       # "rows", "rows+pen", "rows+con+lp", "rows+pen+lp", ...
                 self._graphs.pop(mode, None)
                 self._graph_logits.pop(mode, None)
             if self._captured_mode is not None and self._captured_mode.startswith("rows"):
@@ -390,12 +434,16 @@ class DecodeSession:
         from . import fused_ops
         fused_ops.batch_sample_advance(logits, self.tok.view(-1), self.rows)
 
-    def _step_body(self, greedy: bool, sample: bool = False, rows: bool = False, pen: bool = False, lp: bool = False):
+    def _step_body(self, greedy: bool, sample: bool = False, rows: bool = False, pen: bool = False, lp: bool = False, con: bool = False):
         # invariant on entry: mask is 0 for positions <= write_index (the new position may attend to itself)
         logits = self.model.step(self.tok, self.cache, self.write_index, self.pos, self.mask, last_only=True)
         if pen and (greedy or sample or rows):                  # count the id this step was fed, adjust the logits in place: one launch
             from . import fused_ops                             # in front of the selection (the host-sampled mode adjusts what it gets back)
             fused_ops.logit_penalties(logits[:, -1], self.pen, self.tok.view(-1), self.rows.row_state if rows else None)
+        if con and (greedy or sample or rows):                  # append the id this step was fed, stop / ban on the history: one launch
+            from . import fused_ops                             # behind the penalties', in front of the selection
+            fused_ops.history_constraints(logits[:, -1], self.con, self.tok.view(-1), self.rows.row_state if rows else None,
+                                          self.rows.live if rows else None)
         if rows:                                                # per-row selection, recording, stop + the bookkeeping: one launch;
             from . import fused_ops                             # the tokens live in rows.out_tokens (self.logits is not touched)
             fused_ops.batch_sample_advance(logits[:, -1], self.tok.view(-1), self.rows, self.write_index, self.pos.view(-1),
@@ -474,32 +522,36 @@ class DecodeSession:
         return tuple(key)
 
     @staticmethod
-    def _mode(greedy: bool, sample: bool, rows: bool = False, pen: bool = False, lp: bool = False) -> str:
+    def _mode(greedy: bool, sample: bool, rows: bool = False, pen: bool = False, lp: bool = False, con: bool = False) -> str:
         mode = "rows" if rows else ("sample" if sample else ("greedy" if greedy else "logits"))
         if mode == "logits":                                    # the host decides: it adjusts and records what it gets back
             return mode
-        # "greedy+pen", "sample+lp", "rows+pen+lp", ...: graphs of their own
-        return mode + ("+pen" if pen else "") + ("+lp" if lp else "")
+        # "greedy+pen", "sample+lp", "rows+pen+con+lp", ...: graphs of their own
+        return mode + ("+pen" if pen else "") + ("+con" if con else "") + ("+lp" if lp else "")
 
     @property
     def _captured_greedy(self):                                 # kept for the developer tools that read it
         return self._captured_mode == "greedy"
 
     @torch.no_grad()
-    def capture(self, greedy: bool = True, sample: bool = False, rows: bool = False, pen: bool = False, lp: bool = False):
+    def capture(self, greedy: bool = True, sample: bool = False, rows: bool = False, pen: bool = False, lp: bool = False,
+                con: bool = False):
         """Capture one decode step of the mode - "sample": the device sampler picks the next token, "greedy": the argmax does,
         "rows": the batched generation's per-row kernel does (arm_rows), "logits": the host decides - or keep the captured one while nothing it bakes in has changed.  Graphs of several modes live
         side by side (a decoder that alternates greedy and sampled generations captures each once).  ``pen``: the step with the sampling
         controls' launch (arm_penalties) between lm_head and the selection - "greedy+pen" / "sample+pen" / "rows+pen", captured
         next to the plain ones, which stay as they are.  ``lp``: the step with the log-prob record's launch (arm_logprobs) behind the
-        selection - "greedy+lp", "rows+pen+lp", ... - again graphs of their own."""
+        selection - "greedy+lp", "rows+pen+lp", ... - again graphs of their own.  ``con``: the step with the history constraints' launch
+        (arm_constraints) behind the penalties' and in front of the selection - "greedy+con", "rows+pen+con+lp", ... - likewise."""
         if not self.use_graph:
             return
         from . import _lib
-        mode = self._mode(greedy, sample, rows, pen, lp)
-        pen, lp = "+pen" in mode, mode.endswith("+lp")
+        mode = self._mode(greedy, sample, rows, pen, lp, con)
+        pen, lp, con = "+pen" in mode, mode.endswith("+lp"), "+con" in mode
         if pen and self.pen is None:
             raise RuntimeError("capture(pen=True) before arm_penalties")
+        if con and self.con is None:
+            raise RuntimeError("capture(con=True) before arm_constraints")
         if lp and self.lp is None:
             raise RuntimeError("capture(lp=True) before arm_logprobs")
         if self._graphs:
@@ -518,27 +570,28 @@ class DecodeSession:
         if self.decode_only:
             self.release_prefill_layouts()
         # (the token counts of the sampling controls included: the warm-up runs must not count tokens; and the log-prob record's
-        # entry counts: they must record nothing - what they wrote past the count is overwritten by the steps that follow)
+        # entry counts: they must record nothing - what they wrote past the count is overwritten by the steps that follow; and the
+        # history constraints' lengths: they must append nothing that survives - a row they stop comes back with row_state / live)
         state = ((self.tok, self.write_index, self.pos, self.mask, self.rng_state) + self.rows.tensors()
-                 + (self.pen.tensors() if pen else ()) + ((self.lp.count,) if lp else ()))
+                 + (self.pen.tensors() if pen else ()) + ((self.lp.count,) if lp else ()) + (self.con.tensors() if con else ()))
         saved = tuple(t.clone() for t in state)
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
-            self._step_body(greedy, sample, rows, pen, lp)          # warm-up: allocations, lazy repacks
+            self._step_body(greedy, sample, rows, pen, lp, con)          # warm-up: allocations, lazy repacks
             # the warm-up built what the step reads (e.g. the gate-interleaved copy of w_in): what it made redundant goes now,
             # and the step runs once more so that every pre-bound launch exists before the capture
             if self.decode_only and self.release_prefill_layouts():
-                self._step_body(greedy, sample, rows, pen, lp)
+                self._step_body(greedy, sample, rows, pen, lp, con)
             if self.low_footprint and self.drop_canonical():
-                self._step_body(greedy, sample, rows, pen, lp)      # the pre-bound launches re-validate against the stand-in buffers
+                self._step_body(greedy, sample, rows, pen, lp, con)      # the pre-bound launches re-validate against the stand-in buffers
         torch.cuda.current_stream(self.device).wait_stream(side)
         if self._graphs and self._graph_epoch != _lib.layout_epoch():
             self._graphs.clear()                                # this mode's warm-up rebuilt / dropped a layout the older graphs baked in
             self._graph_logits.clear()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            self._step_body(greedy, sample, rows, pen, lp)
+            self._step_body(greedy, sample, rows, pen, lp, con)
         # capture ran the body twice on live state: restore (the cache rows it touched get rewritten)
         for dst, src in zip(state, saved):
             dst.copy_(src)
@@ -574,7 +627,7 @@ class DecodeSession:
 
     @torch.no_grad()
     def decode_step(self, token: Optional[Tensor] = None, greedy: bool = True, sample: bool = False, rows: bool = False,
-                    pen: bool = False, lp: bool = False) -> Tensor:
+                    pen: bool = False, lp: bool = False, con: bool = False) -> Tensor:
         """Advance by one token.  `token` (batch, 1) overrides the device-resident next id (needed when the
         host samples).  ``sample``: the device sampler (set_sampling) draws the next id into ``tok``.  Returns this step's
         last-position logits (batch, vocab).  ``rows``: the batched generation's step (arm_rows): every row selects, records and
@@ -582,20 +635,22 @@ class DecodeSession:
         count the id fed into the step and adjust the logits in front of the selection; the host-decides mode (neither greedy, sample
         nor rows) returns the logits as the model gave them - its caller adjusts them (``fused_ops.logit_penalties``).  ``lp``: the
         armed log-prob record (arm_logprobs) gets this step's entry behind the selection; the host-decides mode records nothing -
-        its caller does, with the id it chose (``fused_ops.step_logprobs``)."""
+        its caller does, with the id it chose (``fused_ops.step_logprobs``).  ``con``: the armed history constraints
+        (arm_constraints) append the id fed into the step, stop rows (``rows`` only) and ban entries behind the penalties and in
+        front of the selection; the host-decides mode leaves that to its caller too (``fused_ops.history_constraints``)."""
         if self.length + 1 > self.capacity:
             raise ValueError("cache capacity exhausted")
         if token is not None:
             self.tok.copy_(token.to(self.device))
-        mode = self._mode(greedy, sample, rows, pen, lp)
-        pen, lp = "+pen" in mode, mode.endswith("+lp")
+        mode = self._mode(greedy, sample, rows, pen, lp, con)
+        pen, lp, con = "+pen" in mode, mode.endswith("+lp"), "+con" in mode
         if mode in self._graphs:
             from . import _lib
             if self._graph_epoch != _lib.layout_epoch() or self._captured_mode != mode:   # a derived layout was rebuilt / dropped since
-                self.capture(greedy, sample, rows, pen, lp)     # the capture: capture() compares the fingerprint and keeps the graphs
+                self.capture(greedy, sample, rows, pen, lp, con)   # the capture: capture() compares the fingerprint and keeps the graphs
             self.graph.replay()                                 # when only modules of OTHER models / sessions moved (ADVICE r3)
         else:
-            self._step_body(greedy, sample, rows, pen, lp)
+            self._step_body(greedy, sample, rows, pen, lp, con)
         self.length += 1
         self.cache.length = self.length
         return None if rows else self.logits
@@ -826,7 +881,8 @@ class ChatGLMDecoder:
                      prefill_chunk: Optional[int] = None, use_graph: Optional[bool] = None, sync_every_token: bool = True,
                      seed: Optional[int] = None, device_sampler: Optional[bool] = None, repetition_penalty: float = 1.0,
                      presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias: Optional[dict] = None,
-                     logprobs: Optional[int] = None):
+                     logprobs: Optional[int] = None, no_repeat_ngram_size: int = 0, bad_words_ids=None, stop_sequences=None,
+                     min_new_tokens: int = 0):
         """Yields generated token ids one by one (batch 1, like the reference, chatglm_q/decoder.py:70).
 
         Default = the reference's only mode: top-k / top-p sampling (top_k 100, top_p 0.8, temperature 1.0).  On a GPU the
@@ -847,10 +903,28 @@ class ChatGLMDecoder:
         sampling controls, before temperature / top-k / top-p - by one more launch behind the selection inside the captured step.
         The ids are yielded as before; when the generation ends (or the generator is closed) ``last_logprobs`` holds a
         ``GenerationLogprobs`` with one entry per token yielded, read from the device once; ``last_stats["logprobs"]`` says whether
-        the record was on."""
+        the record was on.
+
+        History constraints (defaults: off, the path above exactly): ``no_repeat_ngram_size`` n >= 1 lets no n-gram of prompt +
+        output occur twice (the Hugging Face rule; at most ``fused_ops.CONSTRAINT_SEQ_LEN_MAX``); ``bad_words_ids``, a list of id
+        lists, bans each list's last id while the ids in front of it are the latest ones (a list of one id is banned always; the
+        prompt counts); ``min_new_tokens`` keeps the end token out of the first that many tokens (nothing to do with
+        ``ignore_eos`` or no end token); ``stop_sequences``, a list of id lists, ends the generation once the OUTPUT ends with one
+        of them - the sequence is yielded, then the generator ends, as with the end token.  At most
+        ``fused_ops.CONSTRAINT_SEQS_MAX`` sequences of all kinds together, each of at most ``CONSTRAINT_SEQ_LEN_MAX`` ids.  The bans
+        run as one more launch inside the captured step, behind the penalties' and in front of the selection, on the ordered history
+        kept on the device; stop sequences are matched by the host against the ids it reads anyway.  ``last_stats["constraints"]``
+        says whether any of them was on, ``last_stats["stop_sequence"]`` which stop sequence the output ends with (None: none)."""
         n_lp = check_logprobs(logprobs)
         self.last_logprobs = None
         prefix = list(prefix_ids)
+        from . import fused_ops
+        eos = None if ignore_eos or self.eos_token_id is None else int(self.eos_token_id)
+        # (validated once, up front, all kinds together; the device is armed without the stop sequences: here the host matches them)
+        (n_gram, min_new, table), = fused_ops.ConstraintState.check(1, no_repeat_ngram_size, bad_words_ids, stop_sequences, min_new_tokens,
+                                                                    eos, vocab=self.model.config.vocab_size)
+        stops = [q for kind, q in table if kind == fused_ops.ConstraintState.STOP]
+        con_settings = [(n_gram, min_new, [e for e in table if e[0] != fused_ops.ConstraintState.STOP])]
         limit = min(self.max_sequence_length, self.model.config.max_sequence_length)   # the cache cannot outgrow the rotary table
         budget = min(max_generated_tokens, limit - len(prefix))
         if budget <= 0:
@@ -862,6 +936,7 @@ class ChatGLMDecoder:
         sess.busy = True
         try:
             pen = sess.arm_penalties([prefix], repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
+            con = sess.arm_constraints([prefix], checked=con_settings)
             dev_sample = (not greedy) and sess.device_sampler_serves(top_k) and device_sampler is not False
             if device_sampler and not greedy and not dev_sample:
                 raise ValueError(f"device_sampler=True needs a GPU and top_k <= 1024 (got {sess.device}, top_k {top_k})")
@@ -871,12 +946,12 @@ class ChatGLMDecoder:
                 sess.set_sampling(top_k, top_p, temperature, seed)
             if n_lp is None:
                 yield from self._generate(sess, prefix, budget, top_k, top_p, temperature, greedy, ignore_eos, prefill_chunk,
-                                          sync_every_token, dev_sample, pen)
+                                          sync_every_token, dev_sample, pen, con=con, stops=stops)
             else:
                 sess.arm_logprobs(True)
                 returned = 0
                 inner = self._generate(sess, prefix, budget, top_k, top_p, temperature, greedy, ignore_eos, prefill_chunk,
-                                       sync_every_token, dev_sample, pen, lp=True)
+                                       sync_every_token, dev_sample, pen, lp=True, con=con, stops=stops)
                 try:
                     for token in inner:
                         returned += 1
@@ -892,7 +967,7 @@ class ChatGLMDecoder:
 
     def _generate(self, sess: DecodeSession, prefix, budget: int, top_k: int, top_p: float, temperature: float, greedy: bool,
                   ignore_eos: bool, prefill_chunk: Optional[int], sync_every_token: bool, dev_sample: bool = False, pen: bool = False,
-                  lp: bool = False):
+                  lp: bool = False, con: bool = False, stops=()):
         # `auto`: the device picks the next token inside the step (argmax or the one-launch sampler) and feeds it back itself
         auto = greedy or dev_sample
         times = []
@@ -902,6 +977,8 @@ class ChatGLMDecoder:
         logits = sess.prefill(torch.tensor([prefix], dtype=torch.long), prefill_chunk)
         if pen:                                                    # nothing generated yet: prompt ids and the bias only
             logits = sess.penalize_first(logits)
+        if con:                                                    # ... and the bans the prompt alone decides
+            logits = sess.constrain_first(logits)
         if dev_sample:
             nxt = sess.sample_first(logits)
         else:
@@ -915,23 +992,26 @@ class ChatGLMDecoder:
         generated = [token]
         yield token
 
-        device_loop = auto and not sync_every_token and (ignore_eos or self.eos_token_id is None)
-        if len(generated) < budget and (ignore_eos or token != self.eos_token_id):
+        # a stop sequence ends the generation as the end token does: matched against the ids the host reads anyway, yielded, then the end
+        stopped = (lambda: matched_stop_sequence(generated, stops) is not None) if stops else (lambda: False)
+        # (with stop sequences the host has to see every token: no loop in which it reads nothing until the end)
+        device_loop = auto and not sync_every_token and (ignore_eos or self.eos_token_id is None) and not stops
+        if len(generated) < budget and (ignore_eos or token != self.eos_token_id) and not stopped():
             sess.tok.fill_(token)
-            sess.capture(greedy=greedy, sample=dev_sample, pen=pen, lp=lp)
+            sess.capture(greedy=greedy, sample=dev_sample, pen=pen, lp=lp, con=con)
         pending = []
         # Greedy or device-sampled decoding on a captured step: the graph feeds its own choice back, so step k + 1 does not wait for the HOST to have seen
         # token k.  It is launched before token k is read (one step of speculation: wasted - and harmless, the next prefill re-arms the
         # session - when token k turns out to be the end token), so the device never idles for the host's read-back + launch latency
         # (~20 us of a 1.15 ms token).  Tokens are yielded one by one as before.
         ahead = (auto and not device_loop and sess.graph is not None and sess.device.type == "cuda" and AHEAD_LAUNCH
-                 and len(generated) < budget and (ignore_eos or token != self.eos_token_id))
+                 and len(generated) < budget and (ignore_eos or token != self.eos_token_id) and not stopped())
         if ahead:
             ring = torch.empty((2, 1), dtype=torch.long).pin_memory()
             events = [torch.cuda.Event(), torch.cuda.Event()]
 
             def launch(k):
-                sess.decode_step(None, greedy=greedy, sample=dev_sample, pen=pen, lp=lp)
+                sess.decode_step(None, greedy=greedy, sample=dev_sample, pen=pen, lp=lp, con=con)
                 ring[k & 1].copy_(sess.tok.view(-1), non_blocking=True)
                 events[k & 1].record()
 
@@ -949,23 +1029,27 @@ class ChatGLMDecoder:
                 t0 = now
                 generated.append(token)
                 yield token
-                if not more or (not ignore_eos and token == self.eos_token_id):
+                if not more or (not ignore_eos and token == self.eos_token_id) or stopped():
                     break
                 k += 1
-        while not ahead and len(generated) < budget and (ignore_eos or generated[-1] != self.eos_token_id):
+        while not ahead and len(generated) < budget and (ignore_eos or generated[-1] != self.eos_token_id) and not stopped():
             t0 = time.perf_counter()
             if device_loop:
                 # the graph feeds its own choice back as the next input: the host only replays
-                sess.decode_step(greedy=greedy, sample=dev_sample, pen=pen, lp=lp)
+                sess.decode_step(greedy=greedy, sample=dev_sample, pen=pen, lp=lp, con=con)
                 pending.append(sess.tok.clone())
                 generated.append(-1)
                 times.append(time.perf_counter() - t0)
                 continue
             logits = sess.decode_step(None if auto else torch.tensor([[generated[-1]]]), greedy=greedy, sample=dev_sample, pen=pen,
-                                      lp=lp)
+                                      lp=lp, con=con)
             if pen and not auto:                                   # the host samples: it adjusts the logits it got back (tok = the id just fed)
                 from . import fused_ops
                 logits = fused_ops.logit_penalties(logits if logits.stride(-1) == 1 else logits.contiguous(), sess.pen, sess.tok.view(-1))
+            if con and not auto:                                   # ... and constrains them, behind the penalties
+                from . import fused_ops
+                logits = fused_ops.history_constraints(logits if logits.stride(-1) == 1 else logits.contiguous(), sess.con,
+                                                       sess.tok.view(-1))
             nxt = sess.tok[:, 0] if auto else top_p_sampling(logits, top_k, top_p, temperature)
             if lp and not auto:                                    # ... and records its own choice on the logits it sampled from
                 from . import fused_ops
@@ -989,6 +1073,7 @@ class ChatGLMDecoder:
             "prefix": len(prefix), "generated": n, "init_s": times[0], "sum_s": sum(times),
             "gen_tok_per_s": (n - 1) / rest if n > 1 and rest > 0 else float("nan"),
             "avg_tok_per_s": n / sum(times), "penalties": bool(pen), "logprobs": bool(lp),
+            "constraints": bool(con or stops), "stop_sequence": matched_stop_sequence(generated, stops),
         }
         if self.time_log:
             s = self.last_stats
@@ -1021,7 +1106,8 @@ class ChatGLMDecoder:
     def generate_batch_ids(self, prompts, max_generated_tokens=400, top_k=100, top_p=0.8, temperature=1.0, greedy=False,
                            seed=None, ignore_eos: bool = False, prefill_chunk: Optional[int] = None, use_graph: Optional[bool] = None,
                            poll_every: Optional[int] = None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
-                           logit_bias=None, logprobs: Optional[int] = None):
+                           logit_bias=None, logprobs: Optional[int] = None, no_repeat_ngram_size=0, bad_words_ids=None,
+                           stop_sequences=None, min_new_tokens=0):
         """Generate for a batch of prompts (lists of token ids, any lengths: LEFT padded with 0 as ``score_ids`` pads them) in one
         decode batch; returns one list of generated ids per prompt.  A row that stopped on the end token ends with it, as
         ``generate_ids`` yields it.
@@ -1047,7 +1133,15 @@ class ChatGLMDecoder:
 
         ``logprobs`` (None: off) is ``generate_ids``' as well: with an int n in [0, ``fused_ops.TOP_LOGPROBS_MAX``] the step records
         every row's token log-prob and n alternatives on the device (finished rows record nothing), and ``last_logprobs`` holds one
-        ``GenerationLogprobs`` per prompt, in prompt order, each as long as the row's returned ids."""
+        ``GenerationLogprobs`` per prompt, in prompt order, each as long as the row's returned ids.
+
+        ``no_repeat_ngram_size``, ``bad_words_ids``, ``stop_sequences`` and ``min_new_tokens`` are ``generate_ids``' history constraints,
+        each one value or one per prompt; for the two sequence arguments the nesting depth decides - a list of id lists applies to every
+        row, a list of one such list (or None) per prompt gives every row its own.  They run as one more launch in the captured step on
+        every row's own ordered history.  A row that has generated one of its stop sequences is finished ON THE DEVICE by the step
+        that follows (one row-step is spent on seeing it) and its ids end with the sequence.  Defaults: off, the path above exactly;
+        ``last_stats["constraints"]`` says whether they were active, ``last_stats["stop_sequence"]`` holds, per row, which of its stop
+        sequences its ids end with (None: none)."""
         n_lp = check_logprobs(logprobs)
         self.last_logprobs = None
         prompts = [list(map(int, p)) for p in prompts]
@@ -1090,9 +1184,13 @@ class ChatGLMDecoder:
         pen_args = (per_row("repetition_penalty", repetition_penalty, float), per_row("presence_penalty", presence_penalty, float),
                     per_row("frequency_penalty", frequency_penalty, float), per_row("logit_bias", logit_bias, lambda d: d))
         fused_ops.PenaltyState.check(B, self.model.config.vocab_size, list(zip(*pen_args[:3])), pen_args[3])
+        stop = None if ignore_eos or self.eos_token_id is None else int(self.eos_token_id)
+        con_settings = fused_ops.ConstraintState.check(B, no_repeat_ngram_size, bad_words_ids, stop_sequences, min_new_tokens, stop,
+                                                       vocab=self.model.config.vocab_size)
+        row_stops = [[q for kind, q in table if kind == fused_ops.ConstraintState.STOP] for _, _, table in con_settings]
         if max(budgets) == 0:
             self.last_stats = {"batch": B, "prefix": [len(p) for p in prompts], "generated": [0] * B, "steps": 0, "penalties": False,
-                               "logprobs": n_lp is not None}
+                               "logprobs": n_lp is not None, "constraints": False, "stop_sequence": [None] * B}
             if n_lp is not None:
                 self.last_logprobs = [GenerationLogprobs([], [], []) for _ in prompts]
             return [[] for _ in prompts]
@@ -1102,18 +1200,20 @@ class ChatGLMDecoder:
             ids[b, S - len(p):] = torch.tensor(p, dtype=torch.long)
             attn[b, S - len(p):] = 1
         capacity = min(-(-(S + max(budgets)) // 64) * 64, self.model.config.max_sequence_length)
-        stop = None if ignore_eos or self.eos_token_id is None else int(self.eos_token_id)
         sess = self._session_for(capacity, use_graph, batch=B)
         sess.busy = True
         try:
             sess.arm_rows(list(zip(ks, ps, ts)), seeds, budgets, stop)
             pen = sess.arm_penalties(prompts, *pen_args)
+            con = sess.arm_constraints(prompts, checked=con_settings)
             lp = sess.arm_logprobs(n_lp is not None)
             cuda = sess.device.type == "cuda"
             t0 = time.perf_counter()
             logits = sess.prefill(ids, prefill_chunk, attention_mask=attn)
             if pen:
                 logits = sess.penalize_first(logits, rows=True)
+            if con:
+                logits = sess.constrain_first(logits, rows=True)
             sess.sample_rows_first(logits)
             if lp:
                 sess.logprobs_first(logits, rows=True)
@@ -1121,7 +1221,7 @@ class ChatGLMDecoder:
             t_first = time.perf_counter() - t0
             steps, max_steps = 0, max(budgets) - 1
             if live > 0 and max_steps > 0:
-                sess.capture(greedy=False, rows=True, pen=pen, lp=lp)
+                sess.capture(greedy=False, rows=True, pen=pen, lp=lp, con=con)
                 if cuda:
                     ring = torch.zeros((2, 1 + 2 * B), dtype=torch.int32).pin_memory()
                     events = [torch.cuda.Event(), torch.cuda.Event()]
@@ -1129,7 +1229,7 @@ class ChatGLMDecoder:
                 while steps < max_steps:
                     n = min(poll, max_steps - steps)
                     for _ in range(n):
-                        sess.decode_step(greedy=False, rows=True, pen=pen, lp=lp)
+                        sess.decode_step(greedy=False, rows=True, pen=pen, lp=lp, con=con)
                     steps += n
                     if not cuda:
                         if int(sess.rows.live[0]) == 0:
@@ -1162,6 +1262,7 @@ class ChatGLMDecoder:
             "prefill_s": t_first, "sum_s": total,
             "gen_tok_per_s": (gen - sum(1 for c in counts if c)) / rest if steps and rest > 0 else float("nan"),
             "avg_tok_per_s": gen / total if total > 0 else float("nan"), "penalties": bool(pen), "logprobs": bool(lp),
+            "constraints": bool(con), "stop_sequence": [matched_stop_sequence(res[b], row_stops[b]) for b in range(B)],
         }
         if self.time_log:
             s = self.last_stats

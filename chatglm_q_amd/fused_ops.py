@@ -720,6 +720,258 @@ def logit_penalties(logits: Tensor, state: PenaltyState, tok: Tensor | None = No
     return logits
 
 
+# ---- history constraints: no-repeat n-grams, banned / stop sequences, minimum length (csrc/history_constraints.hip) ------------------
+CONSTRAINT_SEQS_MAX = 32     # sequences of one row, all kinds together (QL_CONSTRAINT_SEQS_MAX, include/qlinear_hip.h); more raise a ValueError
+CONSTRAINT_SEQ_LEN_MAX = 16  # ids of one sequence, and the largest no-repeat n-gram size (QL_CONSTRAINT_SEQ_LEN_MAX)
+
+
+def _is_seq(v) -> bool:
+    return isinstance(v, (list, tuple))
+
+
+def _is_int(v) -> bool:
+    """An integer value of any numeric type (3, 3.0, a numpy integer); None, strings and bools are not."""
+    if isinstance(v, bool) or isinstance(v, str) or v is None:
+        return False
+    try:
+        return int(v) == v
+    except (TypeError, ValueError, OverflowError):
+        return False
+
+
+class ConstraintState:
+    """Static buffers of ``history_constraints`` for a batch of rows (a captured step reads and updates them in place): ``hist``
+    (batch, hist_ld) int32 - every row's real prompt ids, then its generated ids, in order; ``hist_len`` / ``prompt_len`` (batch,)
+    int32; ``cfg`` (batch, 2) int32 = no-repeat n-gram size (0 = off), min_new; and every row's sequence table ``seq_tok`` (batch,
+    CONSTRAINT_SEQS_MAX, CONSTRAINT_SEQ_LEN_MAX) int32, ``seq_len`` / ``seq_kind`` (batch, CONSTRAINT_SEQS_MAX) int32, ``seq_count``
+    (batch,) int32 - kinds BAN (the last id is banned behind the others), STOP (the row finishes once it has generated the sequence)
+    and MIN (one id, banned until min_new tokens are generated).  ``active``: whether the last ``arm`` set anything."""
+    BAN, STOP, MIN = 0, 1, 2
+
+    def __init__(self, batch: int, hist_ld: int, device):
+        if batch < 1 or hist_ld < 1:
+            raise ValueError(f"ConstraintState: batch >= 1 and hist_ld >= 1 (got {batch}, {hist_ld})")
+        self.batch, self.hist_ld, self.device = batch, hist_ld, torch.device(device)
+        i32 = dict(dtype=torch.int32, device=device)
+        self.hist = torch.zeros((batch, hist_ld), **i32)
+        self.hist_len = torch.zeros(batch, **i32)
+        self.prompt_len = torch.zeros(batch, **i32)
+        self.cfg = torch.zeros((batch, 2), **i32)
+        self.seq_tok = torch.zeros((batch, CONSTRAINT_SEQS_MAX, CONSTRAINT_SEQ_LEN_MAX), **i32)
+        self.seq_len = torch.zeros((batch, CONSTRAINT_SEQS_MAX), **i32)
+        self.seq_kind = torch.zeros((batch, CONSTRAINT_SEQS_MAX), **i32)
+        self.seq_count = torch.zeros(batch, **i32)
+        self.active = False
+
+    @staticmethod
+    def per_row(name: str, v, batch: int):
+        """A scalar setting for every row, or one per row."""
+        if _is_seq(v):
+            if len(v) != batch:
+                raise ValueError(f"constraints: {name} has {len(v)} entries for {batch} rows")
+            return list(v)
+        return [v] * batch
+
+    @staticmethod
+    def per_row_sequences(name: str, v, batch: int):
+        """A sequence argument for every row: None, a list of id lists (every row gets it) or a list of ``batch`` such lists (or
+        None) - the nesting depth decides.  Returns one list of id lists per row."""
+        if v is None:
+            return [[] for _ in range(batch)]
+        if not _is_seq(v):
+            raise ValueError(f"constraints: {name} must be a list of token-id lists (got {type(v).__name__})")
+        nested = any(e is None or (_is_seq(e) and len(e) > 0 and _is_seq(e[0])) for e in v)
+        if not nested:
+            if any(not _is_seq(e) for e in v):
+                raise ValueError(f"constraints: {name} must be a list of token-id lists")
+            return [[list(e) for e in v] for _ in range(batch)]
+        if len(v) != batch:
+            raise ValueError(f"constraints: {name} has {len(v)} entries for {batch} rows")
+        out = []
+        for b, e in enumerate(v):
+            if e is not None and (not _is_seq(e) or any(not _is_seq(q) for q in e)):
+                raise ValueError(f"constraints: row {b}: {name} must be a list of token-id lists or None")
+            out.append([] if e is None else [list(q) for q in e])
+        return out
+
+    @staticmethod
+    def check(batch: int, no_repeat_ngram_size=0, bad_words_ids=None, stop_sequences=None, min_new_tokens=0, eos_id=None,
+              vocab: int | None = None):
+        """Validate the four controls - each one value for every row or one per row (the sequence arguments: see
+        ``per_row_sequences``) - and return them normalised: per row ``(n, min_new, [(kind, ids), ...])``, the table in the order
+        BAN, STOP, MIN.  ``min_new_tokens`` with no ``eos_id`` arms nothing.  A ValueError names the offending row."""
+        ns = ConstraintState.per_row("no_repeat_ngram_size", no_repeat_ngram_size, batch)
+        mins = ConstraintState.per_row("min_new_tokens", min_new_tokens, batch)
+        eos = ConstraintState.per_row("eos_id", eos_id, batch)
+        bans = ConstraintState.per_row_sequences("bad_words_ids", bad_words_ids, batch)
+        stops = ConstraintState.per_row_sequences("stop_sequences", stop_sequences, batch)
+        out = []
+        for b in range(batch):
+            n, mn = ns[b], mins[b]
+            if not _is_int(n) or n < 0:
+                raise ValueError(f"constraints: row {b}: no_repeat_ngram_size must be an integer >= 0 (got {n})")
+            if n > CONSTRAINT_SEQ_LEN_MAX:
+                raise ValueError(f"constraints: row {b}: no_repeat_ngram_size {n}, at most {CONSTRAINT_SEQ_LEN_MAX} (CONSTRAINT_SEQ_LEN_MAX)")
+            if not _is_int(mn) or mn < 0 or mn >= 2 ** 31:
+                raise ValueError(f"constraints: row {b}: min_new_tokens must be an integer in [0, 2^31) (got {mn})")
+            table = []
+            for kind, name, seqs in ((ConstraintState.BAN, "bad_words_ids", bans[b]), (ConstraintState.STOP, "stop_sequences", stops[b])):
+                for q in seqs:
+                    if len(q) == 0:
+                        raise ValueError(f"constraints: row {b}: an empty sequence in {name}")
+                    if len(q) > CONSTRAINT_SEQ_LEN_MAX:
+                        raise ValueError(f"constraints: row {b}: a sequence of {len(q)} ids in {name}, at most {CONSTRAINT_SEQ_LEN_MAX} "
+                                         "(CONSTRAINT_SEQ_LEN_MAX)")
+                    for i in q:
+                        if not _is_int(i) or not 0 <= int(i) < (2 ** 31 if vocab is None else vocab):
+                            raise ValueError(f"constraints: row {b}: id {i!r} in {name} outside the vocabulary")
+                    table.append((kind, [int(i) for i in q]))
+            if int(mn) > 0 and eos[b] is not None:
+                e = eos[b]
+                if not _is_int(e) or not 0 <= int(e) < (2 ** 31 if vocab is None else vocab):
+                    raise ValueError(f"constraints: row {b}: eos_id {e} outside the vocabulary")
+                table.append((ConstraintState.MIN, [int(e)]))
+            if len(table) > CONSTRAINT_SEQS_MAX:
+                raise ValueError(f"constraints: row {b}: {len(table)} sequences (banned, stop and the end id of min_new_tokens together), "
+                                 f"at most {CONSTRAINT_SEQS_MAX} (CONSTRAINT_SEQS_MAX)")
+            out.append((int(n), int(mn), table))
+        return out
+
+    @staticmethod
+    def neutral(settings) -> bool:
+        """True when the (validated) settings arm nothing: every row with n = 0 and an empty table."""
+        return all(n == 0 and not table for n, _, table in settings)
+
+    def arm(self, prompts, settings):
+        """Start a generation, in place (the buffers keep their addresses): row b's history becomes ``prompts[b]`` - its REAL prompt
+        ids, no pads - and its controls ``settings[b]`` = ``(n, min_new, [(kind, ids), ...])`` as ``check`` returns them."""
+        B = self.batch
+        if len(prompts) != B or len(settings) != B:
+            raise ValueError(f"ConstraintState.arm: {len(prompts)} prompts and {len(settings)} settings for {B} rows")
+        hist = torch.zeros((B, self.hist_ld), dtype=torch.int32)
+        seq_tok = torch.zeros((B, CONSTRAINT_SEQS_MAX, CONSTRAINT_SEQ_LEN_MAX), dtype=torch.int32)
+        seq_len = torch.zeros((B, CONSTRAINT_SEQS_MAX), dtype=torch.int32)
+        seq_kind = torch.zeros((B, CONSTRAINT_SEQS_MAX), dtype=torch.int32)
+        cfg = torch.zeros((B, 2), dtype=torch.int32)
+        for b, (ids, (n, mn, table)) in enumerate(zip(prompts, settings)):
+            ids = [int(i) for i in ids]
+            if len(ids) > self.hist_ld:
+                raise ValueError(f"ConstraintState.arm: row {b}: a prompt of {len(ids)} ids for a history of {self.hist_ld}")
+            if not 0 <= n <= CONSTRAINT_SEQ_LEN_MAX or mn < 0 or len(table) > CONSTRAINT_SEQS_MAX:
+                raise ValueError(f"ConstraintState.arm: row {b}: settings outside the caps (ConstraintState.check validates them)")
+            if ids:
+                hist[b, :len(ids)] = torch.tensor(ids, dtype=torch.int32)
+            cfg[b, 0], cfg[b, 1] = n, mn
+            for s, (kind, q) in enumerate(table):
+                if not 1 <= len(q) <= CONSTRAINT_SEQ_LEN_MAX or kind not in (self.BAN, self.STOP, self.MIN):
+                    raise ValueError(f"ConstraintState.arm: row {b}: sequence {s} outside the caps (ConstraintState.check validates them)")
+                seq_tok[b, s, :len(q)] = torch.tensor(q, dtype=torch.int32)
+                seq_len[b, s], seq_kind[b, s] = len(q), kind
+        self.hist.copy_(hist)
+        self.hist_len.copy_(torch.tensor([len(p) for p in prompts], dtype=torch.int32))
+        self.prompt_len.copy_(self.hist_len)
+        self.cfg.copy_(cfg)
+        self.seq_tok.copy_(seq_tok)
+        self.seq_len.copy_(seq_len)
+        self.seq_kind.copy_(seq_kind)
+        self.seq_count.copy_(torch.tensor([len(t) for _, _, t in settings], dtype=torch.int32))
+        self.active = not self.neutral(settings)
+        return self
+
+    def tensors(self):
+        """What a step changes and a capture saves and restores (what a warm-up wrote past ``hist_len`` is overwritten by the
+        steps that follow)."""
+        return (self.hist_len,)
+
+
+def _clamp(v: int, lo: int, hi: int) -> int:
+    return lo if v < lo else (hi if v > hi else v)
+
+
+def _history_constraints_host(logits: Tensor, state: ConstraintState, tok, row_state, live):
+    """CPU form of qlinear_history_constraints: rules 0 - 3 of its comment in include/qlinear_hip.h, row by row in Python."""
+    B, N = logits.shape
+    for b in range(B):
+        if row_state is not None and int(row_state[b, 1]) & BatchRows.FINISHED:
+            continue
+        L = _clamp(int(state.hist_len[b]), 0, state.hist_ld)
+        if tok is not None and L < state.hist_ld:
+            t = int(tok[b])
+            state.hist[b, L] = t if -2 ** 31 <= t < 2 ** 31 else -1
+            L += 1
+            state.hist_len[b] = L
+        n = _clamp(int(state.cfg[b, 0]), 0, CONSTRAINT_SEQ_LEN_MAX)
+        min_new = int(state.cfg[b, 1])
+        count = _clamp(int(state.seq_count[b]), 0, CONSTRAINT_SEQS_MAX)
+        if n == 0 and count == 0:
+            continue
+        h = state.hist[b, :L].tolist()
+        g = L - _clamp(int(state.prompt_len[b]), 0, L)
+        table = []
+        for s in range(count):
+            m = _clamp(int(state.seq_len[b, s]), 0, CONSTRAINT_SEQ_LEN_MAX)
+            if m > 0:
+                table.append((int(state.seq_kind[b, s]), state.seq_tok[b, s, :m].tolist()))
+        if row_state is not None and any(kind == ConstraintState.STOP and len(q) <= g and h[L - len(q):] == q for kind, q in table):
+            row_state[b, 1] |= BatchRows.FINISHED
+            live.sub_(1)
+            continue
+        banned = []
+        for kind, q in table:
+            m = len(q)
+            if kind == ConstraintState.BAN and L >= m - 1 and h[L - (m - 1):L] == q[:m - 1]:
+                banned.append(q[m - 1])
+            if kind == ConstraintState.MIN and g < min_new:
+                banned.append(q[0])
+        if n >= 1 and L >= n:
+            w = n - 1
+            key = h[L - w:L]
+            banned.extend(h[i + w] for i in range(L - n + 1) if h[i:i + w] == key)
+        ids = sorted({v for v in banned if 0 <= v < N})
+        if ids:
+            logits[b, torch.tensor(ids, dtype=torch.long)] = float("-inf")
+
+
+def history_constraints(logits: Tensor, state: ConstraintState, tok: Tensor | None = None, row_state: Tensor | None = None,
+                        live: Tensor | None = None) -> Tensor:
+    """Apply ``state``'s no-repeat n-gram rule, banned sequences and minimum length to `logits` (B, N) IN PLACE (-inf into every banned
+    entry), advance the token history and finish rows that have generated a stop sequence, in one launch
+    (``qlinear_history_constraints``, whose comment in include/qlinear_hip.h holds the rules).  ``tok`` (B,) int64: the ids fed into
+    this step, appended first; None (the first token after a prefill): nothing is appended.  ``row_state`` / ``live`` (together or
+    not at all): a ``BatchRows``' - finished rows are left untouched, and stop sequences are evaluated only with them.  Returns
+    `logits`.  CPU tensors take the host form (Python, the same rules)."""
+    if logits.dim() != 2 or logits.shape[1] < 1 or logits.stride(1) != 1:
+        raise ValueError(f"history_constraints: logits must be (B, N) with N >= 1 and unit column stride, got {tuple(logits.shape)}")
+    B, N = logits.shape
+    if B != state.batch:
+        raise ValueError(f"history_constraints: {B} logits rows for a ConstraintState of {state.batch}")
+    if B > 1 and logits.stride(0) < N:
+        raise ValueError("history_constraints: overlapping logits rows")
+    if tok is not None and (tok.dtype != torch.int64 or tok.numel() != B or not tok.is_contiguous()):
+        raise ValueError("history_constraints: tok must be a contiguous int64 tensor of B elements")
+    if (row_state is None) != (live is None):
+        raise ValueError("history_constraints: row_state and live go together")
+    if row_state is not None and (row_state.dtype != torch.int32 or tuple(row_state.shape) != (B, 2) or not row_state.is_contiguous()):
+        raise ValueError("history_constraints: row_state must be a contiguous int32 (B, 2) tensor (BatchRows.row_state)")
+    if live is not None and (live.dtype != torch.int32 or live.numel() != 1):
+        raise ValueError("history_constraints: live must be an int32 tensor of one element (BatchRows.live)")
+    for t in (state.hist, tok, row_state, live):
+        if t is not None and t.device != logits.device:
+            raise ValueError(f"history_constraints: logits on {logits.device}, state on {t.device}")
+    if not logits.is_cuda:
+        _history_constraints_host(logits, state, None if tok is None else tok.view(-1), row_state, live)
+        return logits
+    lib = _lib.get_lib()
+    with torch.cuda.device(logits.device):
+        st = lib.qlinear_history_constraints(logits.data_ptr(), B, N, logits.stride(0) if B > 1 else N, state.hist.data_ptr(),
+                                             state.hist_ld, state.hist_len.data_ptr(), state.prompt_len.data_ptr(), state.cfg.data_ptr(),
+                                             state.seq_tok.data_ptr(), state.seq_len.data_ptr(), state.seq_kind.data_ptr(),
+                                             state.seq_count.data_ptr(), _lib.ptr(tok), _lib.ptr(row_state), _lib.ptr(live),
+                                             _lib.dtype_code(logits.dtype), _lib.stream_ptr(logits.device))
+    _lib.check(st, "qlinear_history_constraints")
+    return logits
+
+
 # ---- log-probabilities during generation: the chosen token's and the most likely alternatives' (csrc/logprob.hip) -------------------------
 TOP_LOGPROBS_MAX = 20        # alternatives one step can record (QL_TOP_LOGPROBS_MAX, include/qlinear_hip.h)
 

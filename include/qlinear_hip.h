@@ -53,7 +53,9 @@ extern "C" {
  * Still 3: qlinear_gptq_block added - purely additive.
  * Still 3: qlinear_step_logprobs (and the constant QL_TOP_LOGPROBS_MAX) added - purely additive; qlinear_token_logprob and the
  * selection entry points are unchanged.
- * Still 3: qlinear_w4g32_onetile_launches and the QLINEAR_DISPATCH family `noonetile` (flag bit 8) added - purely additive. */
+ * Still 3: qlinear_w4g32_onetile_launches and the QLINEAR_DISPATCH family `noonetile` (flag bit 8) added - purely additive.
+ * Still 3: qlinear_history_constraints (and the constants QL_CONSTRAINT_SEQS_MAX, QL_CONSTRAINT_SEQ_LEN_MAX, QL_CONSTRAINT_BAN / _STOP /
+ * _MIN) added - purely additive; qlinear_logit_penalties and the selection entry points are unchanged. */
 #define QLINEAR_ABI_VERSION 3
 
 /* activation dtypes */
@@ -598,6 +600,52 @@ int qlinear_logit_penalties(void* logits, int64_t B, int64_t N, int64_t ldl, con
 int qlinear_step_logprobs(const void* logits, int64_t B, int64_t N, int64_t ldl, const int64_t* tok, const int32_t* row_state,
                           int32_t* count, float* chosen, int32_t* top_ids, float* top_lp, int64_t cap, int64_t n_top, int dtype,
                           void* stream);
+
+/* The controls that depend on the ORDER of a row's tokens, in one launch between lm_head (behind qlinear_logit_penalties when that is
+ * armed) and the selection entry points: no-repeat n-grams, banned multi-token sequences, stop sequences and a minimum length.  Edits
+ * logits (B, N) IN PLACE (row stride ldl, unit column stride); the row's token history is kept in device memory and advanced by this
+ * launch, and every control is read from device memory, so ONE captured graph serves every setting.
+ *   hist (B, hist_ld) int32: row b's real prompt ids (no pads), then its generated ids.  hist_len (B) int32: L, how many of them are
+ *     valid (clamped to [0, hist_ld]).  prompt_len (B) int32: P (clamped to [0, L]); g = L - P tokens have been generated.
+ *   cfg (B, 2) int32: n, the no-repeat n-gram size (0 = off; clamped to [0, QL_CONSTRAINT_SEQ_LEN_MAX]), and min_new.
+ *   seq_tok (B, QL_CONSTRAINT_SEQS_MAX, QL_CONSTRAINT_SEQ_LEN_MAX) int32, seq_len / seq_kind (B, QL_CONSTRAINT_SEQS_MAX) int32,
+ *     seq_count (B) int32: row b's sequence table is its first seq_count[b] entries (clamped to [0, QL_CONSTRAINT_SEQS_MAX]); entry s
+ *     has seq_len ids (clamped to [0, QL_CONSTRAINT_SEQ_LEN_MAX]; 0: the entry is ignored) and a kind, QL_CONSTRAINT_BAN / _STOP / _MIN
+ *     (another value: ignored).  A MIN entry is one id.
+ *   tok (B) int64, nullable: the id fed into this step, as in qlinear_logit_penalties.
+ *   row_state (B, 2) int32 and live (1) int32: qlinear_batch_sample_advance's; nullable TOGETHER.
+ * For row b, in this order:
+ *   0. row_state given and the row's finished bit (bit 0 of [b][1]) set: the row is left entirely untouched - no append, no write.
+ *   1. append: tok given and L < hist_ld: hist[b][L] = tok[b], L += 1 (hist_len is updated).  tok null (the first token after a
+ *      prefill) or L == hist_ld: nothing is appended and the launch goes on with the history as it is.  An id outside [0, N) is stored
+ *      as it is (one that no int32 holds: as -1); it never indexes the logits.
+ *   2. stop (only when row_state is given): a STOP entry of length m <= g with hist[L-m : L] == its ids - the whole match in generated
+ *      tokens - sets the finished bit and takes one off live[0] (one vector atomic, one thread per row); the row's logits stay as they
+ *      are and the row is done.  The match is seen one step after the step that selected the sequence's last id: that step's selection
+ *      for the row is qlinear_batch_sample_advance's fill id, and the row's recorded tokens end with the sequence.
+ *   3. bans: logits[b][id] = -inf (in the logits dtype) for every id in [0, N) that one of these names:
+ *        n >= 1: hist[i+n-1] for every i in [0, L-n] with hist[i : i+n-1] == hist[L-n+1 : L]   (the Hugging Face no-repeat rule; n = 1:
+ *                every id of the history; L < n: none)
+ *        a BAN entry of length m: its last id, when L >= m-1 and hist[L-m+1 : L] == its first m-1 ids   (m = 1: always; the prompt counts)
+ *        a MIN entry: its id, while g < min_new
+ *      An entry no rule names keeps its bits.  Nothing outside [row, row + N) is touched.
+ * One workgroup per row; every thread reads the length and tok[b] itself, and one thread stores the appended id and the new length
+ * behind a workgroup barrier that all threads cross after their own read; several lanes may store the same -inf to one address, no
+ * logit is read.  Every logits index is range-checked in
+ * the thread that stores, every history index is below the clamped L, every table index below the clamped counts.  A row with n = 0 and
+ * no entries appends and returns.  Bound: one launch; 4 x L bytes of history read per row.
+ * QL_ERR_BAD_DTYPE; QL_ERR_BAD_SHAPE for N < 1, ldl < N, hist_ld < 1 or B > 65535; QL_ERR_NULL_POINTER for a missing required buffer, or
+ * for live without row_state or the reverse; QL_ERR_MISALIGNED for logits not aligned to the element size; B == 0 is QL_OK without a
+ * launch. */
+#define QL_CONSTRAINT_SEQS_MAX 32
+#define QL_CONSTRAINT_SEQ_LEN_MAX 16
+#define QL_CONSTRAINT_BAN 0
+#define QL_CONSTRAINT_STOP 1
+#define QL_CONSTRAINT_MIN 2
+int qlinear_history_constraints(void* logits, int64_t B, int64_t N, int64_t ldl, int32_t* hist, int64_t hist_ld, int32_t* hist_len,
+                                const int32_t* prompt_len, const int32_t* cfg, const int32_t* seq_tok, const int32_t* seq_len,
+                                const int32_t* seq_kind, const int32_t* seq_count, const int64_t* tok, int32_t* row_state, int32_t* live,
+                                int dtype, void* stream);
 
 /* GPTQ (chatglm_q/int4/quantizer.py:151-167, chatglm_q/int8/quantizer.py:126-137): the column walk of ONE block of bc <= 128 input
  * columns over all weight rows in one launch.  All arrays fp32 device memory (dtype must be QL_DTYPE_F32).
