@@ -60,6 +60,7 @@ EXPORTS = {
     "qlinear_launch_count": (c_uint64, []),
     "qlinear_last_dispatch": (c_uint64, []),
     "qlinear_w4g32_onetile_launches": (c_uint64, []),
+    "qlinear_w4g32_onetile_kc_launches": (c_uint64, []),
     "qlinear_dispatch_reset": (None, []),
     "qlinear_dispatch_reload": (None, []),
     "qlinear_dispatch_flags": (ctypes.c_uint, []),

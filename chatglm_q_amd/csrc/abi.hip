@@ -95,6 +95,7 @@ const char* qlinear_status_string(int status) {
 uint64_t qlinear_launch_count(void) { return g_launches.load(std::memory_order_relaxed); }
 
 uint64_t qlinear_w4g32_onetile_launches(void) { return w4_gemv_onetile_launches(); }
+uint64_t qlinear_w4g32_onetile_kc_launches(void) { return w4_gemv_onetile_kc_launches(); }
 
 uint64_t qlinear_last_dispatch(void) { return t_dispatch_log; }
 void qlinear_dispatch_reset(void) { t_dispatch_log = 0; }

@@ -97,6 +97,7 @@ int w4_mlp_pair(int dtype, const void* x, const void* ln_weight, float eps, cons
 // w4_engine.hip: the MLP of a one-row decode step as ONE persistent launch (LDS-DMA loader wave + consumer waves per CU, granule
 // hand-off of the row between the projections); bit-equal to w4_packed_fused(PRO_NORM, gate) + w4_packed_residual
 uint64_t w4_gemv_onetile_launches();                          // w4_packed.hip: launches of the one-tile one-row GEMV so far
+uint64_t w4_gemv_onetile_kc_launches();                       // ... of them, by its K-complete geometry
 int w4_gemv_ksplit(int64_t quads, int64_t G);                 // w4_packed.hip: K slices per quad of the one-row GEMV for a shape
 bool w4_mlp_engine_supported(int64_t Na, int64_t Ka, int64_t Nb, int64_t Kb);
 size_t w4_mlp_engine_workspace_bytes(int64_t N_in);

@@ -182,6 +182,7 @@ __device__ unsigned long long ql_tl_slots[kTlWords * kTlWaves];
 #define QL_TL(i) do { tl_t[i] = (unsigned long long)__builtin_amdgcn_s_memrealtime(); } while (0)
 #define QL_TL_DEP(x) asm volatile("" ::"v"(x))
 #define QL_TL_LANDED() do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); QL_TL(2); } while (0)
+#define QL_TL_SAME(i, j) do { tl_t[i] = tl_t[j]; } while (0)   /* a station this geometry does not have: no time of its own */
 #define QL_TL_WRITE() do { \
         if ((threadIdx.x & 63) == 0) { \
             unsigned long long* tl_p = ql_tl_slots + (size_t)kTlWords * (((int)(by * gridDim.x + bx) * 4 + (int)(threadIdx.x >> 6)) & (kTlWaves - 1)); \
@@ -194,6 +195,7 @@ __device__ unsigned long long ql_tl_slots[kTlWords * kTlWaves];
 #define QL_TL(i) do { } while (0)
 #define QL_TL_DEP(x) do { } while (0)
 #define QL_TL_LANDED() do { } while (0)
+#define QL_TL_SAME(i, j) do { } while (0)
 #define QL_TL_WRITE() do { } while (0)
 #endif
 
@@ -231,8 +233,14 @@ constexpr int kChainWords = 16 * (kChainSlots + 3);
 // different waves beyond serialising the atomics on a word).  The wave whose ticket reads WPQ - 1 arrived last: every partner's write
 // was counted ahead of that partner's ticket, so it holds all sums, adds them in the order below and runs the epilogue.  The others
 // are done.  Nothing waits for another wave.  The ticket words are zeroed by thread 0 in front of the staging barrier.
+// KC (LEAN, KS == 2 only; 0 = off, else the columns per wave, 1 or 2): the K-complete geometry.  A wave owns KC WHOLE columns - lane l holds
+// group l of slice 0 and group gs + l of slice 1, gs and the masks of the lanes past a slice's end as above - so no sum ever leaves the
+// wave: no `red` region, no second barrier, no owner wave; lane 0 of every wave with a live column rounds and stores its own.  A block is
+// 4 * KC columns.  Per (column, slice) nothing changes - same loads, same e / o chains, same fma, a wave_sum of its own - and the two
+// slices' sums are added slice 0 + slice 1 as the quad combine adds them: the bits of the tile-loop kernel.  Request order as before:
+// x row, scales (both slices), weight words (column-major, slice 0 then 1), late operands; each word has its own progressive wait.
 template <typename T, int MB, int ACH, int KS, bool STRICT, int VAR = 0, int PRO = PRO_NONE, int CHAIN = 0, bool ONE_TILE = false, int CW = 4,
-          bool LEAN = false, bool TICKET = false>   // ACH: 16-byte A chunks staged per thread; 0 = A from global
+          bool LEAN = false, bool TICKET = false, int KC = 0>   // ACH: 16-byte A chunks staged per thread; 0 = A from global
 __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, const u32x4* __restrict__ Wt,
                                                        const T* __restrict__ Sp, const void* pro_delta,
                                                        const void* pro_ln_weight, int N, int K, int M, int lda32,
@@ -257,6 +265,7 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
     static_assert(!ONE_TILE || (MB == 1 && A_LDS && VAR == 0 && CHAIN == 0), "the one-tile path is the one-row LDS-staged product kernel");
     static_assert(!LEAN || (ONE_TILE && PRO == PRO_NONE), "the lean entry is the plain / residual one-tile forward's");
     static_assert(!TICKET || (ONE_TILE && CW == 2), "tickets are drawn by the two-column waves of a quad");
+    static_assert(KC == 0 || ((KC == 1 || KC == 2) && LEAN && KS == 2 && !TICKET), "K-complete waves: both slices of 1 or 2 columns, lean entry");
     constexpr int WPQ = KS * (4 / CW);         // waves per column quad
     constexpr int QW = 4 / WPQ;                // column quads per block
     constexpr int NC = ONE_TILE ? CW : 4;      // columns per wave
@@ -265,8 +274,9 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
     QL_TL_DECL();
     QL_TL(0);
     const int ks = wave % KS;
-    const int cw0 = CW == 4 ? 0 : (wave % WPQ) / KS * CW;   // first of this wave's columns within its quad
-    const int t_raw = bx * QW + wave / WPQ;
+    const int kc_col = (bx * 4 + wave) * (KC > 0 ? KC : 1);   // K-complete: first of this wave's columns
+    const int cw0 = KC > 0 ? (kc_col & 3) : CW == 4 ? 0 : (wave % WPQ) / KS * CW;   // first of this wave's columns within its quad
+    const int t_raw = KC > 0 ? (kc_col >> 2) : bx * QW + wave / WPQ;
     const bool wave_active = t_raw * 4 < N;
     const int t = wave_active ? t_raw : 0;     // inactive waves shadow quad 0 (they must reach the barriers)
     const int m0 = by * MB;
@@ -332,7 +342,29 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
 
     // (2) two weight tiles in flight before anything waits
     PackedTile16<MB, A_LDS> t0, t1;
-    if constexpr (ONE_TILE) {
+    bool kc_live[2] = {false, false};          // K-complete: this lane's group of slice s lies inside the slice
+    int kc_g[2] = {0, 0};                      // ... and the group it reads (clamped)
+    if constexpr (KC > 0) {
+        // t0.s[s] = the scales of slice s (one 2-byte or one 4-byte load), t0.w[2 c + s] = column c's word of slice s
+        const char* sb = reinterpret_cast<const char*>(Sp);
+        const char* wb = reinterpret_cast<const char*>(Wt);
+        u32 woff[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int g = s * gs + lane;
+            kc_live[s] = g < min(G, (s + 1) * gs);
+            kc_g[s] = kc_live[s] ? g : G - 1;
+            const u32 soff = ((u32)(t * G + kc_g[s]) * 4u + (u32)cw0) * (u32)sizeof(T);
+            woff[s] = ((u32)(t * 4 + cw0) * (u32)G + (u32)kc_g[s]) * 16u;
+            if constexpr (KC == 2) t0.s[s] = *reinterpret_cast<const u32*>(sb + soff);
+            else t0.s[s] = *reinterpret_cast<const uint16_t*>(sb + soff);
+        }
+#pragma unroll
+        for (int c = 0; c < KC; ++c)
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+                t0.w[2 * c + s] = QL_GEMV_W_LOAD(reinterpret_cast<const u32x4*>(wb + (woff[s] + (u32)c * ((u32)G * 16u))));
+    } else if constexpr (ONE_TILE) {
         // the one tile: scales first (needed by every column, so never the last arrival), then this wave's NC weight words
         const int g = g_begin + lane;
         const int gc = g < g_end ? g : G - 1;
@@ -363,6 +395,17 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
     const bool quad_early = MB == 1 && t * 4 + 3 < N && (((uintptr_t)bias | (uintptr_t)resid | (uintptr_t)C) & 7) == 0;
     const int tq = quad_early ? t * 4 : 0;
     u32x2 bias_q = {0u, 0u}, resid_q = {0u, 0u};
+    u32 kc_b[2] = {0u, 0u}, kc_r[2] = {0u, 0u};               // K-complete: the late operands of this wave's own columns, 2-byte loads
+    if constexpr (KC > 0) {
+        if (bias || resid) {                                  // kernel-uniform, behind the weights, never in the tail
+#pragma unroll
+            for (int c = 0; c < KC; ++c) {
+                const bool ok = kc_col + c < N;
+                kc_b[c] = *reinterpret_cast<const uint16_t*>(bias && ok ? bias + kc_col + c : (const T*)Sp);
+                kc_r[c] = *reinterpret_cast<const uint16_t*>(resid && ok ? resid + kc_col + c : (const T*)Sp);
+            }
+        }
+    } else
     if (bias || resid) {                                      // kernel-uniform: plain forwards issue no extra loads
         bias_q = *reinterpret_cast<const u32x2*>((bias && quad_early ? bias : (const T*)Sp) + tq);
         resid_q = *reinterpret_cast<const u32x2*>((resid && quad_early ? resid : (const T*)Sp) + tq);
@@ -473,6 +516,149 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
     }
     QL_TL(1);
 
+    if constexpr (KC > 0) {
+        // everything that needs the activations alone first, under the weights' flight: 8 LDS reads and both slices' activation sums
+        u32 av[2][16];
+        float corr[2] = {0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const u32x4 x = *reinterpret_cast<const u32x4*>(smem + a_chunk_pos(kc_g[s], j) * 16);
+                av[s][4 * j + 0] = x[0];
+                av[s][4 * j + 1] = x[1];
+                av[s][4 * j + 2] = x[2];
+                av[s][4 * j + 3] = x[3];
+            }
+        }
+        if constexpr (!STRICT) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                float e = 0.f, o = 0.f;
+#pragma unroll
+                for (int i = 0; i < 16; i += 2) {
+                    e = SP::dot(SP::kOnes, av[s][i], e);
+                    o = SP::dot(SP::kOnes, av[s][i + 1], o);
+                }
+                corr[s] = SP::offset(e, o);
+                asm volatile("" : "+v"(corr[s]));             // a product of its own, as in the one-tile path below (bf16)
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        // one (column, slice) word: the arithmetic of compute_tile's column loop on one word, one scale (its 16 bits in s16), from zero.
+        // A COPY of that loop's three variants, kept apart so that the kernels that were measured keep their code: change both together.
+        auto word_dots = [&](const u32x4 wd, const u32 s16, const u32 (&a)[16], const float corr_s) -> float {
+            if constexpr (STRICT && Act<T>::code == QL_DTYPE_BF16) {
+                const float sc = SP::lo(s16), m8 = -8.0f * sc;
+                float v = 0.f;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const u32 w = wd[j];
+                    const u32 ev = w & 0x0F0F0F0Fu, od = (w >> 4) & 0x0F0F0F0Fu;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const u32 src = (i & 1) ? od : ev;
+                        const float qe = (float)((src >> (8 * (i >> 1))) & 0xFFu);
+                        const float qo = (float)((src >> (8 * (i >> 1) + 16)) & 0xFFu);
+                        v = SP::dot(pack2<__bf16>(__builtin_fmaf(qe, sc, m8), __builtin_fmaf(qo, sc, m8)), a[4 * j + i], v);
+                    }
+                }
+                return v;
+            } else if constexpr (STRICT) {
+                const h2 k1032 = {(f16)1032.0f, (f16)1032.0f};
+                const h2 kInv16 = {(f16)0.0625f, (f16)0.0625f};
+                const h2 kM72 = {(f16)-72.0f, (f16)-72.0f};
+                u32 k_mask_hi;
+                asm volatile("s_mov_b32 %0, 0x00F000F0" : "=s"(k_mask_hi));
+                const h2 s2 = as_h2(s16 | (s16 << 16));
+                float v = 0.f;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const u32 w = wd[j], w8 = w >> 8;
+                    const h2 w0 = (as_h2((w & k_mask) | k_magic) - k1032) * s2;
+                    const h2 w1 = (as_h2((w & k_mask_hi) | k_magic) * kInv16 + kM72) * s2;
+                    const h2 w2 = (as_h2((w8 & k_mask) | k_magic) - k1032) * s2;
+                    const h2 w3 = (as_h2((w8 & k_mask_hi) | k_magic) * kInv16 + kM72) * s2;
+                    v = __builtin_amdgcn_fdot2(w0, as_h2(a[4 * j + 0]), v, false);
+                    v = __builtin_amdgcn_fdot2(w1, as_h2(a[4 * j + 1]), v, false);
+                    v = __builtin_amdgcn_fdot2(w2, as_h2(a[4 * j + 2]), v, false);
+                    v = __builtin_amdgcn_fdot2(w3, as_h2(a[4 * j + 3]), v, false);
+                }
+                return v;
+            } else {
+                float e = 0.f, o = 0.f;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const u32 w = wd[j];
+                    const u32 wh = w >> 8;
+                    const u32 x0 = (w & k_mask) | k_magic;
+                    const u32 x1 = ((SP::kSplitChains ? w : (w >> 4)) & k_mask_odd) | k_magic;
+                    const u32 x2 = (wh & k_mask) | k_magic;
+                    const u32 x3 = ((SP::kSplitChains ? wh : (w >> 12)) & k_mask_odd) | k_magic;
+                    e = SP::dot(x0, a[4 * j + 0], e);
+                    o = SP::dot(x1, a[4 * j + 1], o);
+                    e = SP::dot(x2, a[4 * j + 2], e);
+                    o = SP::dot(x3, a[4 * j + 3], o);
+                }
+                return __builtin_fmaf(SP::lo(s16), SP::combine(e, o) - corr_s, 0.f);
+            }
+        };
+        float part[KC][2];                                    // one accumulator per (column, slice): never folded, the add order is the combine's
+#pragma unroll
+        for (int c = 0; c < KC; ++c)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const u32 sv = kc_live[s] ? t0.s[s] : 0u;     // out-of-range lanes contribute 0
+                part[c][s] = word_dots(t0.w[2 * c + s], c == 0 ? (sv & 0xFFFFu) : (sv >> 16), av[s], corr[s]);
+                __builtin_amdgcn_sched_barrier(0);            // the next word waits for itself, not before
+                if (2 * c + s == 2 * KC - 2) QL_TL_LANDED();
+            }
+#pragma unroll
+        for (int c = 0; c < KC; ++c) {
+            QL_TL_DEP(part[c][0]);
+            QL_TL_DEP(part[c][1]);
+        }
+        QL_TL(3);
+        // independent DPP chains: the compiler is free to interleave them
+#pragma unroll
+        for (int c = 0; c < KC; ++c)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) part[c][s] = wave_sum(part[c][s]);
+#pragma unroll
+        for (int c = 0; c < KC; ++c) {
+            QL_TL_DEP(part[c][0]);
+            QL_TL_DEP(part[c][1]);
+        }
+        QL_TL(4);
+        QL_TL_SAME(5, 4);                                     // nothing to combine across waves
+        QL_SPAN_END();
+        if (wave_active && lane == 0) {
+            float y[KC];
+#pragma unroll
+            for (int c = 0; c < KC; ++c) {
+                y[c] = Act<T>::round(part[c][0] + part[c][1]);
+                float bq, rq, unused;
+                unpack2<T>(kc_b[c], bq, unused);
+                unpack2<T>(kc_r[c], rq, unused);
+                if (bias) y[c] = resid ? Act<T>::round(y[c] + bq) : y[c] + bq;
+                if (resid) y[c] = y[c] + rq;
+            }
+            if constexpr (KC == 2) {
+                if (kc_col + 1 < N && ((uintptr_t)C & 3) == 0) {
+                    *reinterpret_cast<u32*>(C + kc_col) = pack2<T>(y[0], y[1]);
+                } else {
+                    if (kc_col < N) Act<T>::store(C + kc_col, y[0]);
+                    if (kc_col + 1 < N) Act<T>::store(C + kc_col + 1, y[1]);
+                }
+            } else {
+                if (kc_col < N) Act<T>::store(C + kc_col, y[0]);
+            }
+        }
+        QL_TL(6);
+        QL_TL_WRITE();
+        return;
+    }
+
     float acc[MB][4];
 #pragma unroll
     for (int m = 0; m < MB; ++m)
@@ -520,6 +706,8 @@ __device__ __forceinline__ void w4_packed_gemv_16_body(const T* __restrict__ A, 
             }
             __builtin_amdgcn_sched_barrier(0);
         }
+        // NOTE: the three arithmetic variants below exist a second time, per (column, slice) word, in `word_dots` of the K-complete path
+        // above; both must stay the tile loop's bits - change them together (tests/test_gemv_kcomplete_gpu.py compares bit for bit).
         auto column_done = [&](int c) {                       // one tile: column c + 1 waits for its own weight word, not before
             if constexpr (ONE_TILE) {
                 __builtin_amdgcn_sched_barrier(0);
@@ -855,6 +1043,15 @@ __global__ __launch_bounds__(256, QL_GEMV_MIN_WAVES) void w4_packed_gemv_16_onet
                                                                                           0.f, 0, resid, (int)blockIdx.x, 0);
 }
 
+// ... and its K-complete geometry (body: KC): two K slices, every wave owns KC whole columns and stores them itself.  Same eight arguments.
+template <typename T, int ACH, bool STRICT, int KC>
+__global__ __launch_bounds__(256, QL_GEMV_MIN_WAVES) void w4_packed_gemv_16_onetile_kc_kernel(const T* __restrict__ A, const u32x4* __restrict__ Wt,
+                                                                const T* __restrict__ Sp, int N, int K, const T* __restrict__ bias,
+                                                                T* __restrict__ C, const T* __restrict__ resid) {
+    w4_packed_gemv_16_body<T, 1, ACH, 2, STRICT, 0, PRO_NONE, 0, true, 2, true, false, KC>(A, Wt, Sp, nullptr, nullptr, N, K, 1, 0, bias, C, 0, nullptr,
+                                                                                           0.f, 0, resid, (int)blockIdx.x, 0);
+}
+
 // ---------------------------------------------------------------------------------------------
 // generic dtype kernel (fp32 / bf16): same decomposition, per-nibble dequant, activations from global
 // ---------------------------------------------------------------------------------------------
@@ -1033,6 +1230,8 @@ int w4_gemv_ksplit(int64_t quads, int64_t G) { return choose_ksplit(quads, G); }
 // QLINEAR_DISPATCH=noonetile: the tile-loop kernel instead (bit-equal).
 static std::atomic<uint64_t> g_onetile_launches{0};
 uint64_t w4_gemv_onetile_launches() { return g_onetile_launches.load(std::memory_order_relaxed); }
+static std::atomic<uint64_t> g_onetile_kc_launches{0};       // ... of them, by the K-complete geometry
+uint64_t w4_gemv_onetile_kc_launches() { return g_onetile_kc_launches.load(std::memory_order_relaxed); }
 static bool one_tile_serves(int64_t G, int ks) { return !(dispatch_flags() & QL_D_NOONETILE) && G >= ks && (G + ks - 1) / ks <= 64; }
 // Columns per wave.  Plain / residual forward: 2 where a quad's waves fit one block (profiles/gemv_onetile_ab.txt).  The fused entries
 // redo their prologue in every block, and twice the blocks is what cost w_in 4.3 % before (profiles/r06_gemv_ksplit_bound_ab.txt): 4.
@@ -1053,6 +1252,15 @@ static int one_tile_cw(int ks, bool pro) {
 #endif
 static bool one_tile_lean(int64_t packed_bytes) { return QL_TUNE("QLINEAR_ONETILE_LEAN", QL_ONETILE_LEAN) != 0 && packed_bytes < ((int64_t)1 << 31); }
 static bool one_tile_ticket() { return QL_TUNE("QLINEAR_ONETILE_TICKET", QL_ONETILE_TICKET) != 0; }
+// K-complete geometry of the lean entry at two K slices (profiles/gemv_kcomplete_ab.txt): QL_ONETILE_KC = columns per wave, 1 or 2; 0 = the
+// quad combine of the two-column waves.  Developer library: QLINEAR_ONETILE_KC; the ticket switch goes first (its kernel has no such form).
+#ifndef QL_ONETILE_KC
+#define QL_ONETILE_KC 1
+#endif
+static int one_tile_kc() {
+    const int kc = QL_TUNE("QLINEAR_ONETILE_KC", QL_ONETILE_KC);
+    return kc == 1 || kc == 2 ? kc : 0;
+}
 
 template <typename T, int ACH, int KS, bool STRICT, int PRO, int CW, bool LEAN = false, bool TICKET = false>
 static int launch_16_onetile(const PackedArgs& p, const Prologue& pro) {
@@ -1085,10 +1293,32 @@ constexpr bool kOneTileSwitches = false;
 #endif
 template <typename T, int ACH, int KS, bool STRICT, bool LEAN, bool TICKET>
 static int launch_16_onetile_cw2(const PackedArgs& p) {
-    if constexpr (kOneTileSwitches || ((!LEAN || QL_ONETILE_LEAN != 0) && TICKET == (QL_ONETILE_TICKET != 0)))
+    // (at two slices a K-complete constant takes every call of the lean entry, and the quad combine behind that entry is not built)
+    if constexpr (kOneTileSwitches || ((!LEAN || QL_ONETILE_LEAN != 0) && TICKET == (QL_ONETILE_TICKET != 0) &&
+                                       !(LEAN && !TICKET && KS == 2 && QL_ONETILE_KC != 0)))
         return launch_16_onetile<T, ACH, KS, STRICT, PRO_NONE, 2, LEAN, TICKET>(p, Prologue{nullptr, nullptr, nullptr, 0.f, 0});
     else
         return QL_ERR_UNSUPPORTED;             // not reachable: one_tile_lean() / one_tile_ticket() are these constants in this build
+}
+
+// ... of the K-complete geometry: 4 * KC columns per block, LDS for the staged row alone.  The product library builds the one its
+// constant names, the developer library both.
+template <typename T, int ACH, bool STRICT, int KC>
+static int launch_16_onetile_kc(const PackedArgs& p) {
+    if constexpr (kOneTileSwitches || (QL_ONETILE_LEAN != 0 && QL_ONETILE_TICKET == 0 && KC == QL_ONETILE_KC)) {
+        const int64_t G = p.K / 32, Npad = (p.N + 3) & ~(int64_t)3;
+        const u32x4* Wt = (const u32x4*)p.packed;
+        const T* Sp = (const T*)((const char*)p.packed + Npad * G * 16);
+        dim3 grid((unsigned)((Npad + 4 * KC - 1) / (4 * KC)), 1);
+        const size_t lds = ((size_t)p.K * sizeof(T) + 15) & ~(size_t)15;
+        w4_packed_gemv_16_onetile_kc_kernel<T, ACH, STRICT, KC><<<grid, 256, lds, p.st>>>((const T*)p.A, Wt, Sp, p.N, p.K, (const T*)p.bias, (T*)p.C,
+                                                                                          (const T*)p.resid);
+        g_onetile_launches.fetch_add(1, std::memory_order_relaxed);
+        g_onetile_kc_launches.fetch_add(1, std::memory_order_relaxed);
+        return finish_launch(QL_K_W4_GEMV);
+    } else {
+        return QL_ERR_UNSUPPORTED;             // not reachable: one_tile_kc() is the constant in this build
+    }
 }
 
 template <typename T, int MB, int ACH, int KS, bool STRICT>
@@ -1110,6 +1340,12 @@ static int launch_16(const PackedArgs& p) {
             if constexpr (KS <= 2)
                 if (one_tile_cw(KS, false) == 2) {
                     const bool lean = one_tile_lean(Npad * G * 16), ticket = one_tile_ticket();
+                    if constexpr (KS == 2)
+                        if (lean && !ticket) {
+                            const int kc = one_tile_kc();
+                            if (kc == 1) return launch_16_onetile_kc<T, ACH, STRICT, 1>(p);
+                            if (kc == 2) return launch_16_onetile_kc<T, ACH, STRICT, 2>(p);
+                        }
                     if (lean) return ticket ? launch_16_onetile_cw2<T, ACH, KS, STRICT, true, true>(p) : launch_16_onetile_cw2<T, ACH, KS, STRICT, true, false>(p);
                     return ticket ? launch_16_onetile_cw2<T, ACH, KS, STRICT, false, true>(p) : launch_16_onetile_cw2<T, ACH, KS, STRICT, false, false>(p);
                 }

@@ -55,7 +55,8 @@ extern "C" {
  * selection entry points are unchanged.
  * Still 3: qlinear_w4g32_onetile_launches and the QLINEAR_DISPATCH family `noonetile` (flag bit 8) added - purely additive.
  * Still 3: qlinear_history_constraints (and the constants QL_CONSTRAINT_SEQS_MAX, QL_CONSTRAINT_SEQ_LEN_MAX, QL_CONSTRAINT_BAN / _STOP /
- * _MIN) added - purely additive; qlinear_logit_penalties and the selection entry points are unchanged. */
+ * _MIN) added - purely additive; qlinear_logit_penalties and the selection entry points are unchanged.
+ * Still 3: qlinear_w4g32_onetile_kc_launches added - purely additive. */
 #define QLINEAR_ABI_VERSION 3
 
 /* activation dtypes */
@@ -128,6 +129,8 @@ uint64_t qlinear_last_dispatch(void);
 /* Launches of the one-tile one-row int4g32 GEMV (QL_K_W4_GEMV's straight-line kernel) since the library was loaded: which of the two
  * GEMV kernels served a call is not visible in its family code. */
 uint64_t qlinear_w4g32_onetile_launches(void);
+/* ... of them, launches of its K-complete geometry (two K slices, every wave owns whole columns and stores them itself). */
+uint64_t qlinear_w4g32_onetile_kc_launches(void);
 void qlinear_dispatch_reset(void);
 void qlinear_dispatch_reload(void);   /* parse QLINEAR_DISPATCH again (it is read once, at the first dispatch decision) */
 /* The parsed QLINEAR_DISPATCH switches as the library holds them (bit 0 no256, 1 nopeel, 2 nofewrow, 3 norows4, 4 nogroupattn,

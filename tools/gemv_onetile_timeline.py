@@ -11,6 +11,8 @@ The geometry switches are read once per process, so each configuration runs in a
   tile-loop  QLINEAR_DISPATCH=noonetile (the kernel before the one-tile path)
   cw4        one-tile path, 4 columns per wave        cw2   one-tile path, 2 columns per wave (the default dispatch: lean entry)
   cw2-64bit  cw2 behind the entry with 64-bit addresses       cw2-ticket  cw2 with the arrival-ticket quad combine (station 5: ticket returned)
+  kc1, kc2   K-complete geometry, 1 / 2 whole columns per wave: no combine across waves, so station 5 does not exist - printed as such,
+             and "combined -> stored" is then reduced -> stored
     python tools/gemv_onetile_timeline.py [--configs tile-loop,cw4,cw2] [--K 4096 --N 4096] [--reps 48]
 """
 import argparse
@@ -23,9 +25,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 LIB = os.path.join(ROOT, "chatglm_q_amd", "csrc", "libqlinear_hip_timeline.so")
 STATIONS = ["entry", "staged", "landed", "dots", "reduced", "combined", "stored"]
-CONFIGS = {"tile-loop": {"QLINEAR_DISPATCH": "noonetile"}, "cw4": {"QLINEAR_ONETILE_CW": "4"}, "cw2": {"QLINEAR_ONETILE_CW": "2"},
-           "cw2-64bit": {"QLINEAR_ONETILE_CW": "2", "QLINEAR_ONETILE_LEAN": "0"},
-           "cw2-ticket": {"QLINEAR_ONETILE_CW": "2", "QLINEAR_ONETILE_TICKET": "1"}}
+# every configuration pins QLINEAR_ONETILE_KC: the library's own default is the geometry that ships
+CONFIGS = {"tile-loop": {"QLINEAR_DISPATCH": "noonetile"}, "cw4": {"QLINEAR_ONETILE_CW": "4", "QLINEAR_ONETILE_KC": "0"},
+           "cw2": {"QLINEAR_ONETILE_CW": "2", "QLINEAR_ONETILE_KC": "0"},
+           "cw2-64bit": {"QLINEAR_ONETILE_CW": "2", "QLINEAR_ONETILE_LEAN": "0", "QLINEAR_ONETILE_KC": "0"},
+           "cw2-ticket": {"QLINEAR_ONETILE_CW": "2", "QLINEAR_ONETILE_TICKET": "1", "QLINEAR_ONETILE_KC": "0"},
+           "kc1": {"QLINEAR_ONETILE_CW": "2", "QLINEAR_ONETILE_KC": "1"}, "kc2": {"QLINEAR_ONETILE_CW": "2", "QLINEAR_ONETILE_KC": "2"}}
+KC_OF = {"kc1": 1, "kc2": 2}                # which configurations must be served by the K-complete kernel (checked by its launch counter)
 
 
 def median(v):
@@ -44,6 +50,7 @@ def child(args):
     lib.qlinear_w4g32_fwd_packed.restype, lib.qlinear_w4g32_fwd_packed.argtypes = res, argtypes
     lib.qlinear_timeline_reset_async.argtypes = [ctypes.c_void_p]
     lib.qlinear_timeline_read.argtypes = [ctypes.c_void_p]
+    lib.qlinear_w4g32_onetile_kc_launches.restype = ctypes.c_uint64
     K, N, dev = args.K, args.N, torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(1234)
     packed = []
@@ -63,6 +70,7 @@ def child(args):
     slots = lib.qlinear_timeline_slots()
     host = np.zeros((slots, 8), dtype=np.uint64)
     chip, per_cu, spans, waves = [], [], [], 0
+    kc0 = lib.qlinear_w4g32_onetile_kc_launches()
     for rep in range(args.reps + 4):
         for w in range(16):
             assert launch(rep * 17 + w) == 0
@@ -84,11 +92,18 @@ def child(args):
         per_cu.append(np.median(lasts, axis=0))
         spans.append(t[:, 6].max() - t0)
         n_cu = len(np.unique(cu))
+    kc_launches, launches = lib.qlinear_w4g32_onetile_kc_launches() - kc0, 17 * (args.reps + 4)
+    assert kc_launches in (0, launches), (kc_launches, launches)
+    no_combine = kc_launches > 0               # the K-complete kernel ran: a wave keeps its columns, station 5 does not exist
+    assert no_combine == (args.child in KC_OF), f"{args.child}: the K-complete kernel {'ran' if no_combine else 'did not run'}"
     names = ["entry after first wave's"] + [f"{a} -> {b}" for a, b in zip(STATIONS, STATIONS[1:])] + ["stored after first wave's entry"]
     chip, per_cu = np.median(np.array(chip), axis=0) * tick_ns, np.median(np.array(per_cu), axis=0) * tick_ns
     print(f"## {args.child}: 1x{K}->{N} fp16, {waves} waves on {n_cu} CUs, {args.reps} probed launches, clock tick {tick_ns:.0f} ns")
     print(f"{'interval (ns, median)':34s} {'last wave of the chip':>22s} {'last wave of a CU (median CU)':>30s}")
     for i, nm in enumerate(names):
+        if no_combine and nm == "reduced -> combined":
+            print(f"{nm:34s} {'none':>22s} {'none':>30s}   (no combine across waves: the next row is reduced -> stored)")
+            continue
         print(f"{nm:34s} {chip[i]:22.0f} {per_cu[i]:30.0f}")
     print(f"{'first entry -> last store (span)':34s} {median(spans) * tick_ns:22.0f}")
     sys.stdout.flush()
