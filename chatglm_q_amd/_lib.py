@@ -143,6 +143,8 @@ EXPORTS = {
                                    c_void_p, c_int64, c_int, c_void_p]),
     "qlinear_step_logprobs": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_int64, c_int64, c_int, c_void_p]),
+    "qlinear_beam_advance": (c_int, [c_int64, c_int64] + [c_void_p] * 7 + [c_int64] + [c_void_p] * 13 + [c_int64, c_void_p]),
+    "qlinear_beam_gather": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "qlinear_masked_softmax": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
                                        c_int, c_void_p]),
     "qlinear_silu_mul": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p]),

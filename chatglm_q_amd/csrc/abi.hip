@@ -859,4 +859,29 @@ int qlinear_gptq_block(const float* W, int64_t n_rows, int64_t ldw, int64_t c0, 
     return gptq_block(bits, W, n_rows, ldw, c0, bc, hinv_block, ldh, Q, Err, Loss, scale, lds, (hipStream_t)stream);
 }
 
+int qlinear_beam_advance(int64_t P, int64_t B, const int32_t* cand_ids, const float* cand_lp, int32_t* cand_count, float* beam_score,
+                         int64_t* tok, int32_t* parent, int32_t* trellis, int64_t cap, int32_t* steps, float* fin_score, float* fin_sum,
+                         int32_t* fin_len, int32_t* fin_row, int32_t* fin_count, int32_t* done, int32_t* live, const float* norm,
+                         const int32_t* cfg, int64_t* write_index, int64_t* pos, float* mask, int64_t capacity, void* stream) {
+    if (P < 0 || P > 65535 || B < 1 || B > QL_BEAMS_MAX || cap < 1 || cap >= ((int64_t)1 << 31)) return QL_ERR_BAD_SHAPE;
+    if (P == 0) return QL_OK;
+    if (!cand_ids || !cand_lp || !cand_count || !beam_score || !tok || !parent || !trellis || !steps || !fin_score || !fin_sum || !fin_len ||
+        !fin_row || !fin_count || !done || !live || !norm || !cfg)
+        return QL_ERR_NULL_POINTER;
+    if ((write_index == nullptr) != (pos == nullptr) || (write_index == nullptr) != (mask == nullptr)) return QL_ERR_NULL_POINTER;
+    if (write_index && !fits_i32(capacity)) return QL_ERR_BAD_SHAPE;
+    return beam_advance(P, B, cand_ids, cand_lp, cand_count, beam_score, tok, parent, trellis, cap, steps, fin_score, fin_sum, fin_len, fin_row,
+                        fin_count, done, live, norm, cfg, write_index, pos, mask, capacity, (hipStream_t)stream);
+}
+
+int qlinear_beam_gather(const int64_t* table, int64_t n_buf, int64_t P, int64_t B, int64_t capacity, int64_t pos_bytes, const int32_t* parent,
+                        const int32_t* first, const int64_t* end, void* stream) {
+    if (n_buf < 0 || n_buf > 65535 || P < 0 || P > 65535 || B < 1 || B > QL_BEAMS_MAX || !fits_i32(capacity) || pos_bytes < 2 ||
+        pos_bytes % 2 != 0 || pos_bytes >= ((int64_t)1 << 24))
+        return QL_ERR_BAD_SHAPE;
+    if (n_buf == 0 || P == 0) return QL_OK;
+    if (!table || !parent || !first || !end) return QL_ERR_NULL_POINTER;
+    return beam_gather(table, n_buf, P, B, capacity, pos_bytes, parent, first, end, (hipStream_t)stream);
+}
+
 }  // extern "C"

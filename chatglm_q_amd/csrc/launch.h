@@ -310,6 +310,14 @@ int history_constraints(int dtype, void* logits, int64_t B, int64_t N, int64_t l
                         const int32_t* seq_kind, const int32_t* seq_count, const int64_t* tok, int32_t* row_state, int32_t* live,
                         hipStream_t st);
 
+// beam_search.hip: the cross-beam selection with its hypothesis bookkeeping, and the in-place reorder of the key/value cache by parent beam
+int beam_advance(int64_t P, int64_t B, const int32_t* cand_ids, const float* cand_lp, int32_t* cand_count, float* beam_score, int64_t* tok,
+                 int32_t* parent, int32_t* trellis, int64_t cap, int32_t* steps, float* fin_score, float* fin_sum, int32_t* fin_len,
+                 int32_t* fin_row, int32_t* fin_count, int32_t* done, int32_t* live, const float* norm, const int32_t* cfg,
+                 int64_t* write_index, int64_t* pos, float* mask, int64_t capacity, hipStream_t st);
+int beam_gather(const int64_t* table, int64_t n_buf, int64_t P, int64_t B, int64_t capacity, int64_t pos_bytes, const int32_t* parent,
+                const int32_t* first, const int64_t* end, hipStream_t st);
+
 // gptq.hip: the column walk of one GPTQ block (at most 128 columns) over all weight rows in one launch; fp32
 int gptq_block(int bits, const float* W, int64_t n_rows, int64_t ldw, int64_t c0, int64_t bc, const float* H, int64_t ldh, float* Q,
                float* Err, float* Loss, float* scale, int64_t lds, hipStream_t st);

@@ -82,6 +82,19 @@ class GenerationLogprobs:
         return f"GenerationLogprobs({len(self)} tokens, {len(self.top_ids[0]) if self.top_ids else 0} alternatives)"
 
 
+class BeamHypothesis:
+    """One result of ``ChatGLMDecoder.beam_search_ids``: ``ids`` - the generated ids (ending with the end token when the hypothesis
+    finished on it); ``score`` - ``sum_logprob / len(ids) ** length_penalty``, what the hypotheses are ranked by; ``sum_logprob`` - the
+    sum of the ids' log-probs under the model."""
+    __slots__ = ("ids", "score", "sum_logprob")
+
+    def __init__(self, ids, score, sum_logprob):
+        self.ids, self.score, self.sum_logprob = ids, score, sum_logprob
+
+    def __repr__(self):
+        return f"BeamHypothesis({len(self.ids)} tokens, score {self.score:.6g})"
+
+
 def check_logprobs(logprobs) -> Optional[int]:
     """``logprobs`` of generate_ids / generate_batch_ids: None = off, an int in [0, TOP_LOGPROBS_MAX] = that many alternatives."""
     from .fused_ops import TOP_LOGPROBS_MAX
@@ -154,6 +167,11 @@ class DecodeSession:
         # history constraints (arm_constraints): every row's ordered token history and its no-repeat / banned / stop / minimum-length
         # settings in device memory, read and updated by the "+con" steps.  Allocated by the first constrained generation
         self.con = None
+        # beam search (arm_beams): beam scores, parents, the trellis and the finished heaps in device memory, read and updated by the
+        # "beam" step, and the table of cache buffers its gather reorders.  Allocated by the first beam search
+        self.beams = None
+        self._beam_table = None
+        self._beams_B = None                                    # the beam count the captured "beam" step bakes in
         self.length = 0
         self.busy = False                                       # a generate_ids generator is running on this session
 
@@ -416,6 +434,43 @@ class DecodeSession:
         fused_ops.top_p_sample(lg, self.tok.view(-1), self.rng_state, dev_params=self.sample_params)
         return self.tok.view(-1)
 
+    def arm_beams(self, num_beams: int, eos_id: Optional[int] = None, length_penalty: float = 1.0, early_stopping: bool = True,
+                  first: int = 0):
+        """Arm a beam search over this session's rows (``fused_ops.BeamState.arm``: allocated on first use): ``batch / num_beams``
+        prompts x ``num_beams`` beams, rows g * num_beams ... are prompt g's and must be prefilled with the same left-padded prompt;
+        ``first`` = the prompt length, the first cache position a step's gather moves.  The captured "beam" step bakes the beam count
+        in: a different one drops it."""
+        from . import fused_ops
+        B = int(num_beams)
+        if not 1 <= B <= fused_ops.BEAMS_MAX or self.batch % B:
+            raise ValueError(f"arm_beams: num_beams in [1, {fused_ops.BEAMS_MAX}] dividing the batch of {self.batch} (got {num_beams})")
+        if self.model.config.vocab_size < 2 * B:
+            raise ValueError(f"arm_beams: a vocabulary of {self.model.config.vocab_size} supplies no {2 * B} candidates per row")
+        if self.beams is None:
+            self.beams = fused_ops.BeamState(self.batch, self.capacity, self.device)
+            self._beam_table = fused_ops.BeamGatherTable(list(self.cache.k) + list(self.cache.v))
+        self.beams.arm(self.batch // B, B, eos_id, length_penalty, early_stopping, first)
+        if self._beams_B is not None and self._beams_B != B:
+            self._graphs.pop("beam", None)
+            self._graph_logits.pop("beam", None)
+            if self._captured_mode == "beam":
+                self.graph = self._captured_mode = None
+            self._beams_B = None
+        return self.beams
+
+    def beam_first(self, logits: Tensor) -> None:
+        """The first token of every beam after a prefill (no bookkeeping: prefill armed the step state): the candidates of the
+        prefill's last-position logits, the selection (only a group's first row carries a finite score, so its 2B best ids seed the
+        beams) and, once, the broadcast of every group's first row over the prompt positions [0, S) to its other rows - the step's
+        gather never moves them again."""
+        from . import fused_ops
+        st = self.beams
+        lg = logits if logits.stride(-1) == 1 else logits.contiguous()
+        fused_ops.step_logprobs(lg, self.tok.view(-1), st.cand)
+        fused_ops.beam_advance(st, self.tok.view(-1))
+        lead = (torch.arange(self.batch, dtype=torch.int32) // st.B * st.B).to(self.device)
+        fused_ops.beam_gather(self._beam_table, lead, torch.zeros(1, dtype=torch.int32, device=self.device), self.write_index, st.B)
+
     def arm_rows(self, params, seeds, budgets, stop_id: Optional[int] = None):
         """Arm the batched generation's per-row state (``fused_ops.BatchRows.arm``): one (top_k, top_p, temperature), seed and
         budget per row, and the stop id (None: none).  The captured "rows" step bakes the stop id in: a different one drops it."""
@@ -434,9 +489,17 @@ class DecodeSession:
         from . import fused_ops
         fused_ops.batch_sample_advance(logits, self.tok.view(-1), self.rows)
 
-    def _step_body(self, greedy: bool, sample: bool = False, rows: bool = False, pen: bool = False, lp: bool = False, con: bool = False):
+    def _step_body(self, greedy: bool, sample: bool = False, rows: bool = False, pen: bool = False, lp: bool = False, con: bool = False,
+                   beam: bool = False):
         # invariant on entry: mask is 0 for positions <= write_index (the new position may attend to itself)
         logits = self.model.step(self.tok, self.cache, self.write_index, self.pos, self.mask, last_only=True)
+        if beam:                                                # candidates, cross-beam selection + bookkeeping, cache reorder: three launches
+            from . import fused_ops
+            st = self.beams
+            fused_ops.step_logprobs(logits[:, -1], self.tok.view(-1), st.cand)
+            fused_ops.beam_advance(st, self.tok.view(-1), self.write_index, self.pos.view(-1), self.mask)
+            fused_ops.beam_gather(self._beam_table, st.parent, st.first, self.write_index, st.B)
+            return
         if pen and (greedy or sample or rows):                  # count the id this step was fed, adjust the logits in place: one launch
             from . import fused_ops                             # in front of the selection (the host-sampled mode adjusts what it gets back)
             fused_ops.logit_penalties(logits[:, -1], self.pen, self.tok.view(-1), self.rows.row_state if rows else None)
@@ -522,7 +585,10 @@ class DecodeSession:
         return tuple(key)
 
     @staticmethod
-    def _mode(greedy: bool, sample: bool, rows: bool = False, pen: bool = False, lp: bool = False, con: bool = False) -> str:
+    def _mode(greedy: bool, sample: bool, rows: bool = False, pen: bool = False, lp: bool = False, con: bool = False,
+              beam: bool = False) -> str:
+        if beam:                                                # the beam search's step: no sampling controls, no record
+            return "beam"
         mode = "rows" if rows else ("sample" if sample else ("greedy" if greedy else "logits"))
         if mode == "logits":                                    # the host decides: it adjusts and records what it gets back
             return mode
@@ -535,19 +601,24 @@ class DecodeSession:
 
     @torch.no_grad()
     def capture(self, greedy: bool = True, sample: bool = False, rows: bool = False, pen: bool = False, lp: bool = False,
-                con: bool = False):
+                con: bool = False, beam: bool = False):
         """Capture one decode step of the mode - "sample": the device sampler picks the next token, "greedy": the argmax does,
         "rows": the batched generation's per-row kernel does (arm_rows), "logits": the host decides - or keep the captured one while nothing it bakes in has changed.  Graphs of several modes live
         side by side (a decoder that alternates greedy and sampled generations captures each once).  ``pen``: the step with the sampling
         controls' launch (arm_penalties) between lm_head and the selection - "greedy+pen" / "sample+pen" / "rows+pen", captured
         next to the plain ones, which stay as they are.  ``lp``: the step with the log-prob record's launch (arm_logprobs) behind the
         selection - "greedy+lp", "rows+pen+lp", ... - again graphs of their own.  ``con``: the step with the history constraints' launch
-        (arm_constraints) behind the penalties' and in front of the selection - "greedy+con", "rows+pen+con+lp", ... - likewise."""
+        (arm_constraints) behind the penalties' and in front of the selection - "greedy+con", "rows+pen+con+lp", ... - likewise.
+        ``beam``: the beam search's step (arm_beams) - "beam", captured next to the others."""
         if not self.use_graph:
             return
         from . import _lib
-        mode = self._mode(greedy, sample, rows, pen, lp, con)
+        mode = self._mode(greedy, sample, rows, pen, lp, con, beam)
         pen, lp, con = "+pen" in mode, mode.endswith("+lp"), "+con" in mode
+        if beam:
+            greedy = sample = rows = False
+            if self.beams is None or self.beams.B < 1:
+                raise RuntimeError("capture(beam=True) before arm_beams")
         if pen and self.pen is None:
             raise RuntimeError("capture(pen=True) before arm_penalties")
         if con and self.con is None:
@@ -573,34 +644,41 @@ class DecodeSession:
         # entry counts: they must record nothing - what they wrote past the count is overwritten by the steps that follow; and the
         # history constraints' lengths: they must append nothing that survives - a row they stop comes back with row_state / live)
         state = ((self.tok, self.write_index, self.pos, self.mask, self.rng_state) + self.rows.tensors()
-                 + (self.pen.tensors() if pen else ()) + ((self.lp.count,) if lp else ()) + (self.con.tensors() if con else ()))
+                 + (self.pen.tensors() if pen else ()) + ((self.lp.count,) if lp else ()) + (self.con.tensors() if con else ())
+                 + (self.beams.tensors() + (self.beams.first,) if beam else ()))
         saved = tuple(t.clone() for t in state)
+        if beam:
+            # the warm-up's gathers touch only cache positions its own steps write, [write_index now, write_index then): every one of
+            # them is written again by a real step before it is read, whatever the parents of the warm-up are
+            self.beams.first.copy_(self.write_index.to(torch.int32))
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
-            self._step_body(greedy, sample, rows, pen, lp, con)          # warm-up: allocations, lazy repacks
+            self._step_body(greedy, sample, rows, pen, lp, con, beam)          # warm-up: allocations, lazy repacks
             # the warm-up built what the step reads (e.g. the gate-interleaved copy of w_in): what it made redundant goes now,
             # and the step runs once more so that every pre-bound launch exists before the capture
             if self.decode_only and self.release_prefill_layouts():
-                self._step_body(greedy, sample, rows, pen, lp, con)
+                self._step_body(greedy, sample, rows, pen, lp, con, beam)
             if self.low_footprint and self.drop_canonical():
-                self._step_body(greedy, sample, rows, pen, lp, con)      # the pre-bound launches re-validate against the stand-in buffers
+                self._step_body(greedy, sample, rows, pen, lp, con, beam)      # the pre-bound launches re-validate against the stand-in buffers
         torch.cuda.current_stream(self.device).wait_stream(side)
         if self._graphs and self._graph_epoch != _lib.layout_epoch():
             self._graphs.clear()                                # this mode's warm-up rebuilt / dropped a layout the older graphs baked in
             self._graph_logits.clear()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            self._step_body(greedy, sample, rows, pen, lp, con)
+            self._step_body(greedy, sample, rows, pen, lp, con, beam)
         # capture ran the body twice on live state: restore (the cache rows it touched get rewritten)
         for dst, src in zip(state, saved):
             dst.copy_(src)
         if rows:
             self._rows_stop = self.rows.stop_id
+        if beam:
+            self._beams_B = self.beams.B
         self._graphs[mode] = graph
         # every graph writes a logits buffer of its own: kept with the graph and bound again whenever its mode comes back
         # ("rows" steps do not publish theirs)
-        self._graph_logits[mode] = None if rows else self.logits
+        self._graph_logits[mode] = None if rows or beam else self.logits
         self.graph, self._captured_mode = graph, mode
         self._graph_key = self._layout_fingerprint()            # AFTER the warm-up built the lazy layouts
         self._graph_epoch, self._graph_versions = _lib.layout_epoch(), self._canonical_versions()
@@ -627,7 +705,7 @@ class DecodeSession:
 
     @torch.no_grad()
     def decode_step(self, token: Optional[Tensor] = None, greedy: bool = True, sample: bool = False, rows: bool = False,
-                    pen: bool = False, lp: bool = False, con: bool = False) -> Tensor:
+                    pen: bool = False, lp: bool = False, con: bool = False, beam: bool = False) -> Tensor:
         """Advance by one token.  `token` (batch, 1) overrides the device-resident next id (needed when the
         host samples).  ``sample``: the device sampler (set_sampling) draws the next id into ``tok``.  Returns this step's
         last-position logits (batch, vocab).  ``rows``: the batched generation's step (arm_rows): every row selects, records and
@@ -637,23 +715,25 @@ class DecodeSession:
         armed log-prob record (arm_logprobs) gets this step's entry behind the selection; the host-decides mode records nothing -
         its caller does, with the id it chose (``fused_ops.step_logprobs``).  ``con``: the armed history constraints
         (arm_constraints) append the id fed into the step, stop rows (``rows`` only) and ban entries behind the penalties and in
-        front of the selection; the host-decides mode leaves that to its caller too (``fused_ops.history_constraints``)."""
+        front of the selection; the host-decides mode leaves that to its caller too (``fused_ops.history_constraints``).  ``beam``:
+        the beam search's step (arm_beams): every row's candidates, the cross-beam selection and the cache reorder by parent beam;
+        returns None (the beams are in ``beams``)."""
         if self.length + 1 > self.capacity:
             raise ValueError("cache capacity exhausted")
         if token is not None:
             self.tok.copy_(token.to(self.device))
-        mode = self._mode(greedy, sample, rows, pen, lp, con)
+        mode = self._mode(greedy, sample, rows, pen, lp, con, beam)
         pen, lp, con = "+pen" in mode, mode.endswith("+lp"), "+con" in mode
         if mode in self._graphs:
             from . import _lib
             if self._graph_epoch != _lib.layout_epoch() or self._captured_mode != mode:   # a derived layout was rebuilt / dropped since
-                self.capture(greedy, sample, rows, pen, lp, con)   # the capture: capture() compares the fingerprint and keeps the graphs
+                self.capture(greedy, sample, rows, pen, lp, con, beam)   # the capture: capture() compares the fingerprint and keeps the graphs
             self.graph.replay()                                 # when only modules of OTHER models / sessions moved (ADVICE r3)
         else:
-            self._step_body(greedy, sample, rows, pen, lp, con)
+            self._step_body(greedy, sample, rows, pen, lp, con, beam)
         self.length += 1
         self.cache.length = self.length
-        return None if rows else self.logits
+        return None if rows or beam else self.logits
 
 
 class SentencePieceIds:
@@ -1273,6 +1353,165 @@ class ChatGLMDecoder:
             print(f"  gen: {s['gen_tok_per_s']:.6f} tok/s")
             print(f"  avg: {s['avg_tok_per_s']:.6f} tok/s")
         return res
+
+    @torch.no_grad()
+    def beam_search_ids(self, prompts, num_beams: int = 4, max_generated_tokens: int = 400, length_penalty: float = 1.0,
+                        early_stopping: bool = True, num_return_sequences: int = 1, ignore_eos: bool = False,
+                        prefill_chunk: Optional[int] = None, use_graph: Optional[bool] = None, poll_every: Optional[int] = None):
+        """Beam search for one prompt (a list of token ids) or a list of prompts (any lengths: LEFT padded with 0) in one decode batch of
+        ``len(prompts) * num_beams`` rows; returns, per prompt, a list of at most ``num_return_sequences`` ``BeamHypothesis(ids, score,
+        sum_logprob)``, the best first (for a single id list: that prompt's list).
+
+        Every step runs on the device inside the captured decode step - the rows' ``2 * num_beams`` best ids (``step_logprobs``' walk),
+        the cross-beam selection with its finished-hypothesis heap (``qlinear_beam_advance``) and the reorder of the key/value cache by
+        parent beam, in place (``qlinear_beam_gather``): three launches behind the model's.  The host replays the step in groups of
+        ``poll_every`` (default BATCH_POLL_EVERY) and looks at the count of prompts still searching, as ``generate_batch_ids`` does; the
+        sequences are never copied on the device - a (token, parent) trellis is read once at the end and walked backwards.
+
+        The rules (tests/_beam_oracle.py): a hypothesis' score is ``sum_logprob / length ** length_penalty``; an end token among a
+        prompt's ``num_beams`` best candidates finishes a hypothesis; ``early_stopping=True`` ends a prompt's search once ``num_beams``
+        hypotheses are finished, ``False`` once additionally none of the running beams can beat the worst of them at the current
+        length.  A prompt still searching when the budget ``min(max_generated_tokens, limit - S)`` runs out (S = the longest prompt,
+        limit = the maximum sequence length) adds its running beams as hypotheses.  A budget of 0 returns ``[]`` per prompt.  With
+        ``ignore_eos`` (or no end token) nothing finishes early.  ``num_beams=1`` is greedy decoding.  Sampling, penalties, logit bias,
+        log-prob records and history constraints are not part of a beam search."""
+        from . import fused_ops
+        single = len(prompts) > 0 and not isinstance(prompts[0], (list, tuple))
+        prompts = [list(map(int, p)) for p in ([prompts] if single else prompts)]
+        if not prompts or any(len(p) == 0 for p in prompts):
+            raise ValueError("beam_search_ids: at least one prompt, none of them empty")
+        if isinstance(num_beams, bool) or not isinstance(num_beams, int) or not 1 <= num_beams <= fused_ops.BEAMS_MAX:
+            raise ValueError(f"beam_search_ids: num_beams must be an int in [1, {fused_ops.BEAMS_MAX}] (got {num_beams!r})")
+        if isinstance(num_return_sequences, bool) or not isinstance(num_return_sequences, int) or not 1 <= num_return_sequences <= num_beams:
+            raise ValueError(f"beam_search_ids: num_return_sequences must be an int in [1, num_beams] (got {num_return_sequences!r})")
+        vocab = self.model.config.vocab_size
+        if vocab < 2 * num_beams:
+            raise ValueError(f"beam_search_ids: a vocabulary of {vocab} supplies no {2 * num_beams} candidates per beam")
+        fused_ops.beam_norm_table(1, length_penalty)            # (validates the penalty)
+        poll = self.BATCH_POLL_EVERY if poll_every is None else int(poll_every)
+        if poll < 1:
+            raise ValueError("beam_search_ids: poll_every >= 1")
+        P, B = len(prompts), num_beams
+        R = P * B
+        S = max(len(p) for p in prompts)
+        limit = min(self.max_sequence_length, self.model.config.max_sequence_length)
+        if S > limit:
+            raise ValueError(f"beam_search_ids: a prompt of {S} tokens exceeds the maximum sequence length {limit}")
+        budget = max(0, min(int(max_generated_tokens), limit - S))
+        eos = None if ignore_eos or self.eos_token_id is None else int(self.eos_token_id)
+        if budget == 0:
+            self.last_stats = {"prompts": P, "beams": B, "prefix": [len(p) for p in prompts], "steps": 0}
+            return [] if single else [[] for _ in prompts]
+        ids = torch.zeros((R, S), dtype=torch.long)
+        attn = torch.zeros((R, S), dtype=torch.long)
+        for g, p in enumerate(prompts):
+            ids[g * B:(g + 1) * B, S - len(p):] = torch.tensor(p, dtype=torch.long)
+            attn[g * B:(g + 1) * B, S - len(p):] = 1
+        capacity = min(-(-(S + budget) // 64) * 64, self.model.config.max_sequence_length)
+        sess = self._session_for(capacity, use_graph, batch=R) if R != 1 else self._session_for(capacity, use_graph)
+        sess.busy = True
+        try:
+            st = sess.arm_beams(B, eos, length_penalty, early_stopping, first=S)
+            cuda = sess.device.type == "cuda"
+            t0 = time.perf_counter()
+            logits = sess.prefill(ids, prefill_chunk, attention_mask=attn)
+            sess.beam_first(logits)
+            live = int(st.live.item())                          # the sync that makes the first-token time valid
+            t_first = time.perf_counter() - t0
+            steps, max_steps = 0, budget - 1
+            if live > 0 and max_steps > 0:
+                sess.capture(greedy=False, beam=True)
+                if cuda:
+                    ring = torch.zeros((2, 1), dtype=torch.int32).pin_memory()
+                    events = [torch.cuda.Event(), torch.cuda.Event()]
+                g = 0
+                while steps < max_steps:
+                    n = min(poll, max_steps - steps)
+                    for _ in range(n):
+                        sess.decode_step(greedy=False, beam=True)
+                    steps += n
+                    if not cuda:
+                        if int(st.live[0]) == 0:
+                            break
+                        continue
+                    ring[g & 1].copy_(st.live, non_blocking=True)
+                    events[g & 1].record()
+                    # the previous group's count: its event is behind the group the device is running now
+                    if g > 0:
+                        events[(g - 1) & 1].synchronize()
+                        if int(ring[(g - 1) & 1, 0]) == 0:
+                            break
+                    g += 1
+            host = st.fetch()                                   # one copy of every buffer at the end
+            norm = st.norm.cpu()
+            total = time.perf_counter() - t0
+        finally:
+            sess.busy = False
+        res = self._beam_results(host, norm, P, B, eos, num_return_sequences)
+        rest = total - t_first
+        self.last_stats = {
+            "prompts": P, "beams": B, "prefix": [len(p) for p in prompts], "steps": steps,
+            "searched": [int(host["steps"][g]) for g in range(P)], "done": [bool(int(host["done"][g])) for g in range(P)],
+            "prefill_s": t_first, "sum_s": total, "steps_per_s": steps / rest if steps and rest > 0 else float("nan"),
+        }
+        if self.time_log:
+            s = self.last_stats
+            print("Decoder (beam search):")
+            print(f"  len: {P} prompts x {B} beams, {max(s['prefix'])}(longest prefix), {s['steps']} steps")
+            print(f" init: {s['prefill_s']:.6f} s")
+            print(f"  sum: {s['sum_s']:.6f} s")
+            print(f"  gen: {s['steps_per_s']:.6f} steps/s")
+        return res[0] if single else res
+
+    @staticmethod
+    def _beam_results(host, norm, P: int, B: int, eos, n_return: int):
+        """The budget end on the host: a group that is not done adds its running beams under the heap rule; per prompt the hypotheses
+        are sorted by score descending, then earlier finish step, then lower slot, and walked back through the trellis."""
+        trellis = host["trellis"]
+
+        def backtrack(row, slots):
+            ids = []
+            for s in range(slots - 1, -1, -1):
+                tok, row = int(trellis[s, row, 0]), int(trellis[s, row, 1])
+                ids.append(tok)
+            return ids[::-1]
+
+        out = []
+        for g in range(P):
+            r0, cnt, t = g * B, int(host["fin_count"][g]), int(host["steps"][g])
+            heap = [(host["fin_score"][r0 + s], int(host["fin_len"][r0 + s]), int(host["fin_row"][r0 + s]), host["fin_sum"][r0 + s], True)
+                    for s in range(cnt)]
+            if not int(host["done"][g]) and t > 0:
+                for r in range(r0, r0 + B):
+                    entry = (host["beam_score"][r] / norm[t], t, r, host["beam_score"][r], False)     # one fp32 division
+                    if len(heap) < B:
+                        heap.append(entry)
+                        continue
+                    worst = 0
+                    for s in range(1, B):
+                        if bool(heap[s][0] <= heap[worst][0]):
+                            worst = s
+                    if bool(entry[0] > heap[worst][0]):
+                        heap[worst] = entry
+            key = [float("-inf") if bool(torch.isnan(e[0])) else float(e[0]) for e in heap]
+            order = sorted(range(len(heap)), key=lambda s: (-key[s], heap[s][1], s))
+            hyps = []
+            for s in order[:n_return]:
+                score, n, row, total, ended = heap[s]
+                ids = backtrack(row, n - 1) + [int(eos)] if ended else backtrack(row, n)
+                hyps.append(BeamHypothesis(ids, float(score), float(total)))
+            out.append(hyps)
+        return out
+
+    def beam_search(self, texts, **kw):
+        """Text interface of ``beam_search_ids`` when a tokenizer (``encode`` / ``decode``) was supplied: per prompt a list of
+        ``(text, score)``, the best first (for a single string: that prompt's list)."""
+        if self.tokenizer is None:
+            raise RuntimeError("no tokenizer: use beam_search_ids() with token ids")
+        single = isinstance(texts, str)
+        outs = self.beam_search_ids([self.tokenizer.encode(t) for t in ([texts] if single else texts)], **kw)
+        res = [[(self.tokenizer.decode(h.ids), h.score) for h in hyps] for hyps in outs]
+        return res[0] if single else res
 
     def generate_batch(self, prefix_texts, **kw):
         """Text interface of ``generate_batch_ids`` when a tokenizer (``encode`` / ``decode``) was supplied: one decoded text per

@@ -1077,6 +1077,254 @@ def step_logprobs(logits: Tensor, tok: Tensor, state: StepLogprobs, row_state: T
     return None
 
 
+# ---- beam search: cross-beam selection and the cache reorder by parent beam (csrc/beam_search.hip) ---------------------------------
+BEAMS_MAX = 10               # QL_BEAMS_MAX (include/qlinear_hip.h): a row supplies 2 * num_beams <= TOP_LOGPROBS_MAX candidates
+
+
+def beam_norm_table(cap: int, length_penalty: float) -> Tensor:
+    """norm[len] = float32(float64(len) ** length_penalty) for len = 0 .. cap: the device divides by it and never calls powf."""
+    lp = float(length_penalty)
+    if not _finite(lp):
+        raise ValueError(f"beam search: length_penalty must be finite (got {length_penalty})")
+    zero = 1.0 if lp == 0 else (0.0 if lp > 0 else float("inf"))
+    return torch.tensor([zero] + [float(n) ** lp for n in range(1, cap + 1)], dtype=torch.float64).float()
+
+
+class BeamState:
+    """Static device buffers of a beam search over ``rows`` = P prompts x B beams batch rows (a captured step reads and updates them in
+    place; rows g*B .. g*B+B-1 are group g): ``beam_score`` (rows,) float32 - the running beams' summed log-probs; ``parent`` (rows,)
+    int32 - the row every row's beam came from in the last step; ``trellis`` (cap, rows, 2) int32 - (token, parent row) per step and
+    row, read once at the end; ``steps`` / ``fin_count`` / ``done`` (rows,) int32, the first P entries used - per group the steps taken,
+    the finished hypotheses held and whether the group is done; ``fin_score`` / ``fin_sum`` (rows,) float32 and ``fin_len`` / ``fin_row``
+    (rows,) int32, read as (P, B) - the finished heap: normalised score, summed log-prob, length and parent row; ``live`` (1,) int32 -
+    groups not done; ``norm`` (cap + 1,) float32 - len ** length_penalty; ``cfg`` (2,) int32 - end id (-1: none), early_stopping;
+    ``first`` (1,) int32 - the first cache position the step's gather moves (the prompt length); ``cand`` - the one-slot ``StepLogprobs``
+    record (2B alternatives) that supplies every row's candidates, reallocated when B changes."""
+
+    def __init__(self, rows: int, cap: int, device):
+        if rows < 1 or cap < 1:
+            raise ValueError(f"BeamState: rows >= 1 and cap >= 1 (got {rows}, {cap})")
+        self.rows, self.cap, self.device = rows, cap, torch.device(device)
+        f32, i32 = dict(dtype=torch.float32, device=device), dict(dtype=torch.int32, device=device)
+        self.beam_score = torch.zeros(rows, **f32)
+        self.parent = torch.arange(rows, **i32)
+        self.trellis = torch.zeros((cap, rows, 2), **i32)
+        self.steps, self.fin_count, self.done = (torch.zeros(rows, **i32) for _ in range(3))
+        self.fin_score, self.fin_sum = torch.zeros(rows, **f32), torch.zeros(rows, **f32)
+        self.fin_len, self.fin_row = torch.zeros(rows, **i32), torch.zeros(rows, **i32)
+        self.live = torch.zeros(1, **i32)
+        self.norm = torch.ones(cap + 1, **f32)
+        self.cfg = torch.zeros(2, **i32)
+        self.first = torch.zeros(1, **i32)
+        self.cand = None
+        self.P = self.B = 0
+        self.eos = -1
+
+    def arm(self, P: int, B: int, eos=None, length_penalty: float = 1.0, early_stopping: bool = True, first: int = 0):
+        """Start a search of P prompts x B beams, in place (the buffers keep their addresses; only ``cand`` is reallocated when B
+        changes): scores 0 for every group's first row and -inf for the others, nothing finished, nothing recorded."""
+        if not 1 <= B <= BEAMS_MAX:
+            raise ValueError(f"BeamState.arm: num_beams must be in [1, {BEAMS_MAX}] (got {B})")
+        if P < 1 or P * B != self.rows:
+            raise ValueError(f"BeamState.arm: {P} prompts x {B} beams for a state of {self.rows} rows")
+        if not 0 <= int(first) <= 2 ** 31 - 1:
+            raise ValueError(f"BeamState.arm: first must be a cache position (got {first})")
+        norm = beam_norm_table(self.cap, length_penalty)
+        if self.cand is None or B != self.B:
+            self.cand = StepLogprobs(self.rows, 1, self.device, n_top=2 * B)
+        self.cand.arm()
+        self.P, self.B = P, B
+        self.eos = -1 if eos is None or int(eos) < 0 else int(eos)
+        score = torch.full((self.rows,), float("-inf"), dtype=torch.float32)
+        score[::B] = 0.0
+        self.beam_score.copy_(score)
+        self.parent.copy_(torch.arange(self.rows, dtype=torch.int32))
+        for t in (self.steps, self.fin_count, self.done, self.fin_score, self.fin_sum, self.fin_len, self.fin_row):
+            t.zero_()
+        self.live.fill_(P)
+        self.norm.copy_(norm)
+        self.cfg.copy_(torch.tensor([self.eos, 1 if early_stopping else 0], dtype=torch.int32))
+        self.first.fill_(int(first))
+        return self
+
+    def tensors(self):
+        """What a step changes besides the trellis (a capture saves and restores it; the trellis slots its warm-up runs write are
+        written again by the steps that follow)."""
+        return (self.beam_score, self.parent, self.steps, self.fin_count, self.done, self.fin_score, self.fin_sum, self.fin_len,
+                self.fin_row, self.live, self.cand.count)
+
+    def fetch(self) -> dict:
+        """Everything the host needs at the end of a search, one copy per buffer."""
+        names = ("beam_score", "parent", "trellis", "steps", "fin_count", "done", "fin_score", "fin_sum", "fin_len", "fin_row", "live")
+        return {k: getattr(self, k).cpu() for k in names}
+
+
+def _beam_advance_host(state: BeamState, tok: Tensor, write_index, pos, mask):
+    """CPU form of qlinear_beam_advance: the same rules, every score one fp32 torch operation."""
+    P, B = state.P, state.B
+    eos, early = int(state.cfg[0]), bool(int(state.cfg[1]))
+    ids, lps = state.cand.top_ids[:, 0], state.cand.top_lp[:, 0]
+    neg = torch.tensor(float("-inf"), dtype=torch.float32)
+    for g in range(P):
+        r0 = g * B
+        st = int(state.steps[g])
+        state.cand.count[r0:r0 + B] = 0
+        if int(state.done[g]) != 0 or st >= state.cap:
+            tok[r0:r0 + B] = eos if eos >= 0 else 0
+            state.parent[r0:r0 + B] = torch.arange(r0, r0 + B, dtype=torch.int32)
+            continue
+        scores = (state.beam_score[r0:r0 + B, None] + lps[r0:r0 + B]).reshape(-1)            # one fp32 add each
+        keys = torch.where(torch.isnan(scores), neg, scores).tolist()
+        order = sorted(range(B * 2 * B), key=lambda c: (-keys[c], c))[:2 * B]
+        t = st + 1
+        nrm = state.norm[t]
+        cnt = int(state.fin_count[g])
+        heap = state.fin_score[r0:r0 + B]
+
+        def worst_slot():
+            worst = 0
+            for q in range(1, B):
+                if bool(heap[q] <= heap[worst]):
+                    worst = q
+            return worst
+
+        nxt = []
+        for j, c in enumerate(order):
+            if len(nxt) == B:
+                break
+            sc, i, r = scores[c], int(ids.reshape(-1)[r0 * 2 * B + c]), r0 + c // (2 * B)
+            if eos >= 0 and i == eos:
+                if j < B:
+                    hs = sc / nrm
+                    slot = -1
+                    if cnt < B:
+                        slot, cnt = cnt, cnt + 1
+                    else:
+                        w = worst_slot()
+                        if bool(hs > heap[w]):
+                            slot = w
+                    if slot >= 0:
+                        state.fin_score[r0 + slot], state.fin_sum[r0 + slot] = hs, sc
+                        state.fin_len[r0 + slot], state.fin_row[r0 + slot] = t, r
+                continue
+            nxt.append((i, r, sc))
+        while len(nxt) < B:                                      # (cannot happen with 2B candidates per row)
+            nxt.append((eos if eos >= 0 else 0, r0 + len(nxt), neg))
+        state.fin_count[g] = cnt
+        fin = cnt == B
+        if fin and not early:
+            fin = bool(heap[worst_slot()] >= nxt[0][2] / nrm)
+        for n, (i, r, sc) in enumerate(nxt):
+            tok[r0 + n], state.parent[r0 + n], state.beam_score[r0 + n] = i, r, sc
+            state.trellis[st, r0 + n, 0], state.trellis[st, r0 + n, 1] = i, r
+        state.steps[g] = t
+        if fin:
+            state.done[g] = 1
+            state.live.sub_(1)
+    if write_index is not None:
+        write_index.add_(1)
+        pos.add_(1)
+        nw = int(write_index.view(-1)[0])
+        if 0 <= nw < mask.shape[-1]:
+            mask[..., nw] = 0.0
+
+
+def beam_advance(state: BeamState, tok: Tensor, write_index: Tensor | None = None, pos: Tensor | None = None, mask: Tensor | None = None):
+    """One beam step's cross-beam selection in one launch (``qlinear_beam_advance``; the rules: include/qlinear_hip.h and
+    tests/_beam_oracle.py) from the candidates ``step_logprobs(logits, tok, state.cand)`` has just recorded: the merge of every group's
+    B x 2B candidates, the walk, the finished heap, done / ``live``, the trellis append, the next ``tok`` (rows,) int64, ``parent`` and
+    ``beam_score``.  With write_index / pos / mask (all or none) the decode step's bookkeeping is done as ``greedy_advance`` does it.
+    CPU tensors take the host form (the same rules bit for bit)."""
+    if state.B < 1 or state.cand is None:
+        raise ValueError("beam_advance: the BeamState is not armed")
+    R = state.rows
+    if tok.dtype != torch.int64 or tok.numel() != R or not tok.is_contiguous():
+        raise ValueError(f"beam_advance: tok must be a contiguous int64 tensor of {R} elements")
+    book = (write_index is not None, pos is not None, mask is not None)
+    if any(book) and not all(book):
+        raise ValueError("beam_advance: write_index, pos and mask go together")
+    if all(book):
+        if write_index.dtype != torch.int64 or pos.dtype != torch.int64 or pos.numel() != R or not pos.is_contiguous():
+            raise ValueError(f"beam_advance: write_index and pos must be int64, pos of {R} elements")
+        if mask.dtype != torch.float32 or mask.numel() != R * mask.shape[-1] or not mask.is_contiguous():
+            raise ValueError(f"beam_advance: mask must be a contiguous fp32 ({R}, 1, capacity) tensor")
+    for t in (tok, write_index, pos, mask):
+        if t is not None and t.device != state.beam_score.device:
+            raise ValueError(f"beam_advance: state on {state.beam_score.device}, step tensors on {t.device}")
+    if not tok.is_cuda:
+        _beam_advance_host(state, tok.view(-1), write_index, pos, mask)
+        return None
+    lib = _lib.get_lib()
+    c = state.cand
+    with torch.cuda.device(tok.device):
+        st = lib.qlinear_beam_advance(state.P, state.B, c.top_ids.data_ptr(), c.top_lp.data_ptr(), c.count.data_ptr(),
+                                      state.beam_score.data_ptr(), tok.data_ptr(), state.parent.data_ptr(), state.trellis.data_ptr(),
+                                      state.cap, state.steps.data_ptr(), state.fin_score.data_ptr(), state.fin_sum.data_ptr(),
+                                      state.fin_len.data_ptr(), state.fin_row.data_ptr(), state.fin_count.data_ptr(), state.done.data_ptr(),
+                                      state.live.data_ptr(), state.norm.data_ptr(), state.cfg.data_ptr(), _lib.ptr(write_index), _lib.ptr(pos),
+                                      _lib.ptr(mask), mask.shape[-1] if mask is not None else 0, _lib.stream_ptr(tok.device))
+    _lib.check(st, "qlinear_beam_advance")
+    return None
+
+
+class BeamGatherTable:
+    """The buffers one ``beam_gather`` launch reorders: tensors of one shape (rows, capacity, ...), dtype and device, each contiguous -
+    a session's ``cache.k`` and ``cache.v`` of every layer (any other per-row, per-position state of that layout can be added) - and,
+    on a GPU, the device table of their base addresses.  The tensors are kept alive with the table."""
+
+    def __init__(self, buffers):
+        buffers = list(buffers)
+        if not buffers:
+            raise ValueError("BeamGatherTable: at least one buffer")
+        b0 = buffers[0]
+        if b0.dim() < 2:
+            raise ValueError("BeamGatherTable: buffers must be (rows, capacity, ...)")
+        for b in buffers:
+            if b.shape != b0.shape or b.dtype != b0.dtype or b.device != b0.device or not b.is_contiguous():
+                raise ValueError("BeamGatherTable: every buffer must be contiguous, of one shape, dtype and device")
+        self.buffers = buffers
+        self.rows, self.capacity = int(b0.shape[0]), int(b0.shape[1])
+        self.pos_bytes = (b0[0, 0].numel() if b0.dim() > 2 else 1) * b0.element_size()
+        if self.pos_bytes < 2 or self.pos_bytes % 2:
+            raise ValueError(f"BeamGatherTable: a position of {self.pos_bytes} bytes (an even size of at least 2 is served)")
+        chunk = 16 if self.pos_bytes % 16 == 0 else (4 if self.pos_bytes % 4 == 0 else 2)
+        if any(b.data_ptr() % chunk for b in buffers):
+            raise ValueError(f"BeamGatherTable: every buffer must be aligned to {chunk} bytes")
+        self.device = b0.device
+        self.table = torch.tensor([b.data_ptr() for b in buffers], dtype=torch.int64).to(b0.device) if b0.is_cuda else None
+
+
+def beam_gather(table: BeamGatherTable, parent: Tensor, first: Tensor, end: Tensor, num_beams: int) -> None:
+    """Reorder every buffer of ``table`` by parent beam IN PLACE, in one launch (``qlinear_beam_gather``): ``buf[r, p] = buf[parent[r],
+    p]`` for every row r and every position p in [first[0], end[0]) (clamped to the capacity).  ``parent`` (rows,) int32 - absolute
+    rows, clamped to the row's own group of ``num_beams`` rows; ``first`` (1,) int32 and ``end`` (1,) int64 live on the device, so one
+    captured launch serves every range.  CPU tensors take an ``index_select`` copy."""
+    B = int(num_beams)
+    if not 1 <= B <= BEAMS_MAX or table.rows % B:
+        raise ValueError(f"beam_gather: num_beams in [1, {BEAMS_MAX}] dividing the {table.rows} rows (got {num_beams})")
+    if parent.dtype != torch.int32 or parent.numel() != table.rows or not parent.is_contiguous():
+        raise ValueError(f"beam_gather: parent must be a contiguous int32 tensor of {table.rows} elements")
+    if first.dtype != torch.int32 or first.numel() != 1 or end.dtype != torch.int64 or end.numel() != 1:
+        raise ValueError("beam_gather: first must be int32[1] and end int64[1]")
+    for t in (parent, first, end):
+        if t.device != table.device:
+            raise ValueError(f"beam_gather: buffers on {table.device}, arguments on {t.device}")
+    if table.table is None:
+        lo, hi = max(int(first.view(-1)[0]), 0), min(int(end.view(-1)[0]), table.capacity)
+        base = torch.arange(table.rows, dtype=torch.int64) // B * B
+        src = base + (parent.view(-1).long() - base).clamp(0, B - 1)
+        if lo < hi and not torch.equal(src, torch.arange(table.rows)):
+            for b in table.buffers:
+                b[:, lo:hi] = b.index_select(0, src)[:, lo:hi]
+        return None
+    lib = _lib.get_lib()
+    with torch.cuda.device(table.device):
+        st = lib.qlinear_beam_gather(table.table.data_ptr(), len(table.buffers), table.rows // B, B, table.capacity, table.pos_bytes,
+                                     parent.data_ptr(), first.data_ptr(), end.data_ptr(), _lib.stream_ptr(table.device))
+    _lib.check(st, "qlinear_beam_gather")
+    return None
+
+
 # ---- GPTQ: the column walk of one block (csrc/gptq.hip) ------------------------------------------------------------------------------
 GPTQ_MAX_BLOCK = 128
 

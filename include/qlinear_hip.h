@@ -56,7 +56,9 @@ extern "C" {
  * Still 3: qlinear_w4g32_onetile_launches and the QLINEAR_DISPATCH family `noonetile` (flag bit 8) added - purely additive.
  * Still 3: qlinear_history_constraints (and the constants QL_CONSTRAINT_SEQS_MAX, QL_CONSTRAINT_SEQ_LEN_MAX, QL_CONSTRAINT_BAN / _STOP /
  * _MIN) added - purely additive; qlinear_logit_penalties and the selection entry points are unchanged.
- * Still 3: qlinear_w4g32_onetile_kc_launches added - purely additive. */
+ * Still 3: qlinear_w4g32_onetile_kc_launches added - purely additive.
+ * Still 3: qlinear_beam_advance and qlinear_beam_gather (and the constant QL_BEAMS_MAX) added - purely additive; qlinear_step_logprobs, which
+ * supplies their candidates, is unchanged. */
 #define QLINEAR_ABI_VERSION 3
 
 /* activation dtypes */
@@ -649,6 +651,53 @@ int qlinear_history_constraints(void* logits, int64_t B, int64_t N, int64_t ldl,
                                 const int32_t* prompt_len, const int32_t* cfg, const int32_t* seq_tok, const int32_t* seq_len,
                                 const int32_t* seq_kind, const int32_t* seq_count, const int64_t* tok, int32_t* row_state, int32_t* live,
                                 int dtype, void* stream);
+
+/* Beam search inside the decode step.  P prompts x B beams (1 <= B <= QL_BEAMS_MAX) are R = P * B batch rows; rows g*B .. g*B+B-1 are
+ * group g, every row of a group holds the same prompt.  A beam step is the model step's launches plus three: qlinear_step_logprobs on a
+ * one-slot record per row (cap = 1, n_top = 2B: the row's 2B best ids and their log-probs lp, 2B <= QL_TOP_LOGPROBS_MAX), then
+ * qlinear_beam_advance, then qlinear_beam_gather.  All state is device memory, so one captured graph serves every search of the same B.
+ *
+ * qlinear_beam_advance - one workgroup per group:
+ *   cand_ids / cand_lp (R, 2B) int32 / float32: the record step_logprobs wrote; cand_count (R) int32: its counts, reset to 0 here.
+ *   beam_score (R) float32: the running beams' summed log-probs (armed 0 for a group's first row, -inf for the others: the first step
+ *     expands beam 0 only).  tok (R) int64, parent (R) int32 (absolute row): written.  trellis (cap, R, 2) int32: (token, parent row) per
+ *     row and step.  steps (P) int32: steps taken.  fin_score / fin_sum (P, B) float32, fin_len / fin_row (P, B) int32, fin_count (P) int32:
+ *     the heap of finished hypotheses (normalised score, raw score, length, parent row).  done (P) int32; live (1) int32: groups not done.
+ *     norm (cap + 1) float32: norm[len] = len ** length_penalty, built on the host.  cfg (2) int32: the end id (< 0: none), early_stopping.
+ *   A group with done != 0 or steps >= cap rides along: tok = the end id (0 without one), parent = the row itself, nothing else changes.
+ *   Otherwise, every operation one correctly rounded fp32 operation, t = steps + 1:
+ *     merge: score = beam_score[row] + lp; the group's B * 2B candidates ordered by score descending (a NaN ranks as -inf), then row
+ *            ascending, then in-row rank ascending; the first 2B are walked in order, until B running beams are filled:
+ *     walk:  the end id at merged rank < B: a finished hypothesis (score / norm[t], score, t, row); at rank >= B: skipped; any other id: the
+ *            next running beam (tok, parent = the candidate's row, beam_score = score).
+ *     heap:  appended while fin_count < B; otherwise it replaces the worst entry (lowest score, on ties the highest slot) when its score
+ *            is strictly greater.
+ *     done:  early_stopping: fin_count == B; otherwise fin_count == B and the worst entry's score >= best new beam_score / norm[t].  A
+ *            group that becomes done takes one off live[0] (one vector atomic); this step's beams are still written.
+ *     trellis[steps][row] = (tok, parent) for the group's rows; steps = t.
+ *   write_index (1) int64, pos (R) int64, mask (R, capacity) float32, nullable TOGETHER: the decode step's bookkeeping exactly as
+ *   qlinear_greedy_advance does it (pos += 1, write_index += 1, the new position unmasked in every row), for done groups as well.
+ *   Every index is bounded by the arguments: trellis slot < cap, norm index <= cap, heap slot < B.
+ *   QL_ERR_BAD_SHAPE for B outside [1, QL_BEAMS_MAX], P > 65535, cap < 1; QL_ERR_NULL_POINTER for a missing buffer or an incomplete
+ *   bookkeeping triple; P == 0 is QL_OK without a launch.
+ *
+ * qlinear_beam_gather - the reorder of the key/value cache by parent beam, IN PLACE (a captured graph and pre-bound launches hold the
+ * buffers' addresses): for every buffer of table (n_buf device int64 base addresses; layout (R, capacity, pos_bytes)), every position p in
+ * [max(first[0], 0), min(end[0], capacity)) and every row r: buf[r][p] = buf[parent[r]][p].  first (1) int32 and end (1) int64 are device
+ * memory (end: the step's write index, already advanced).  parent values are clamped to the row's own group, so no table content can
+ * address outside the buffers.  A thread owns one chunk (16 bytes; 4 or 2 when pos_bytes is no multiple of 16 / 4) of one position across
+ * the B rows of a group, loads all B, then stores the rows that change: cycles and duplicates in parent are safe.  A group whose parents
+ * are the identity reads parent and exits.  The grid is fixed by capacity; workgroups past the range exit.  Every base address must be
+ * aligned to the chunk size.
+ *   QL_ERR_BAD_SHAPE for B outside [1, QL_BEAMS_MAX], P or n_buf > 65535, capacity < 1, pos_bytes < 2 or odd; QL_ERR_NULL_POINTER; n_buf == 0
+ *   or P == 0 is QL_OK without a launch. */
+#define QL_BEAMS_MAX 10
+int qlinear_beam_advance(int64_t P, int64_t B, const int32_t* cand_ids, const float* cand_lp, int32_t* cand_count, float* beam_score,
+                         int64_t* tok, int32_t* parent, int32_t* trellis, int64_t cap, int32_t* steps, float* fin_score, float* fin_sum,
+                         int32_t* fin_len, int32_t* fin_row, int32_t* fin_count, int32_t* done, int32_t* live, const float* norm,
+                         const int32_t* cfg, int64_t* write_index, int64_t* pos, float* mask, int64_t capacity, void* stream);
+int qlinear_beam_gather(const int64_t* table, int64_t n_buf, int64_t P, int64_t B, int64_t capacity, int64_t pos_bytes, const int32_t* parent,
+                        const int32_t* first, const int64_t* end, void* stream);
 
 /* GPTQ (chatglm_q/int4/quantizer.py:151-167, chatglm_q/int8/quantizer.py:126-137): the column walk of ONE block of bc <= 128 input
  * columns over all weight rows in one launch.  All arrays fp32 device memory (dtype must be QL_DTYPE_F32).
