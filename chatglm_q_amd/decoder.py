@@ -167,6 +167,10 @@ class DecodeSession:
         # history constraints (arm_constraints): every row's ordered token history and its no-repeat / banned / stop / minimum-length
         # settings in device memory, read and updated by the "+con" steps.  Allocated by the first constrained generation
         self.con = None
+        # regex-constrained generation (arm_grammar): the vocabulary's byte table, every row's automaton and its current state in device
+        # memory, read and advanced by the "+gr" steps.  Allocated by the first generation with a grammar
+        self.gr = None
+        self._gr_source = None                                  # the TokenBytes the GrammarState was built from
         # beam search (arm_beams): beam scores, parents, the trellis and the finished heaps in device memory, read and updated by the
         # "beam" step, and the table of cache buffers its gather reorders.  Allocated by the first beam search
         self.beams = None
@@ -408,6 +412,45 @@ class DecodeSession:
         lg = logits if logits.stride(-1) == 1 else logits.contiguous()
         return fused_ops.history_constraints(lg, self.con, None, self.rows.row_state if rows else None, self.rows.live if rows else None)
 
+    def arm_grammar(self, grammars, eos_id=None, token_bytes=None) -> bool:
+        """Arm the grammars for a new generation (``fused_ops.GrammarState.arm``): ``grammars`` = one ``grammar.ByteDFA`` / pattern string /
+        None for every row, or one per row (None: the row is unconstrained); ``eos_id``: the id a row may choose exactly when its
+        output is a full match (one, or one per row; None: none).  ``token_bytes`` (``grammar.TokenBytes``): the vocabulary's byte
+        table - needed by the first armed generation, kept afterwards; a different one replaces the buffers and drops the "+gr" graphs.
+        Every state starts at 0.  Returns whether any row has a grammar; with none nothing is armed - and nothing allocated - and the
+        generation takes the steps without the launch."""
+        from . import fused_ops
+        from .grammar import as_dfa
+        B = self.batch
+        dfas = [None if g is None else as_dfa(g) for g in fused_ops.ConstraintState.per_row("grammar", grammars, B)]
+        if all(d is None for d in dfas):
+            if self.gr is not None:
+                self.gr.active = False
+            return False
+        dfas, eos = fused_ops.GrammarState.check(B, dfas, eos_id, vocab=self.model.config.vocab_size)
+        if token_bytes is None and self.gr is None:
+            raise ValueError("arm_grammar: a grammar needs the vocabulary's byte table (token_bytes=, grammar.token_byte_table builds one)")
+        if self.gr is None or (token_bytes is not None and token_bytes is not self._gr_source):
+            if self.gr is not None:                             # other buffers: the graphs that baked the old ones in go
+                for mode in [m for m in self._graphs if "+gr" in m]:
+                    self._graphs.pop(mode, None)
+                    self._graph_logits.pop(mode, None)
+                if self._captured_mode is not None and "+gr" in self._captured_mode:
+                    self.graph = self._captured_mode = None
+            vocab = self.model.config.vocab_size
+            table = token_bytes.padded(vocab) if len(token_bytes) < vocab else token_bytes   # a padded vocabulary's extra ids are empty
+            self.gr = fused_ops.GrammarState(B, table, self.device)
+            self._gr_source = token_bytes
+        self.gr.arm(dfas, eos)
+        return True
+
+    def grammar_first(self, logits: Tensor, rows: bool = False) -> Tensor:
+        """The armed grammars applied in place to a prefill's last-position logits (nothing generated yet: every state stays at its
+        start) - behind ``constrain_first``, in front of the first selection."""
+        from . import fused_ops
+        lg = logits if logits.stride(-1) == 1 else logits.contiguous()
+        return fused_ops.grammar_mask(lg, self.gr, None, self.rows.row_state if rows else None)
+
     def arm_logprobs(self, on: bool = True) -> bool:
         """Arm the log-prob record for a new generation (``fused_ops.StepLogprobs``: allocated on first use, one entry per cache
         position, TOP_LOGPROBS_MAX alternatives wide) - nothing recorded yet.  ``on`` False: nothing is armed or allocated and the
@@ -490,7 +533,7 @@ class DecodeSession:
         fused_ops.batch_sample_advance(logits, self.tok.view(-1), self.rows)
 
     def _step_body(self, greedy: bool, sample: bool = False, rows: bool = False, pen: bool = False, lp: bool = False, con: bool = False,
-                   beam: bool = False):
+                   beam: bool = False, gr: bool = False):
         # invariant on entry: mask is 0 for positions <= write_index (the new position may attend to itself)
         logits = self.model.step(self.tok, self.cache, self.write_index, self.pos, self.mask, last_only=True)
         if beam:                                                # candidates, cross-beam selection + bookkeeping, cache reorder: three launches
@@ -507,6 +550,9 @@ class DecodeSession:
             from . import fused_ops                             # behind the penalties', in front of the selection
             fused_ops.history_constraints(logits[:, -1], self.con, self.tok.view(-1), self.rows.row_state if rows else None,
                                           self.rows.live if rows else None)
+        if gr and (greedy or sample or rows):                   # walk the id this step was fed, mask what the automaton does not survive:
+            from . import fused_ops                             # one launch behind the history constraints', in front of the selection
+            fused_ops.grammar_mask(logits[:, -1], self.gr, self.tok.view(-1), self.rows.row_state if rows else None)
         if rows:                                                # per-row selection, recording, stop + the bookkeeping: one launch;
             from . import fused_ops                             # the tokens live in rows.out_tokens (self.logits is not touched)
             fused_ops.batch_sample_advance(logits[:, -1], self.tok.view(-1), self.rows, self.write_index, self.pos.view(-1),
@@ -586,14 +632,14 @@ class DecodeSession:
 
     @staticmethod
     def _mode(greedy: bool, sample: bool, rows: bool = False, pen: bool = False, lp: bool = False, con: bool = False,
-              beam: bool = False) -> str:
+              beam: bool = False, gr: bool = False) -> str:
         if beam:                                                # the beam search's step: no sampling controls, no record
             return "beam"
         mode = "rows" if rows else ("sample" if sample else ("greedy" if greedy else "logits"))
         if mode == "logits":                                    # the host decides: it adjusts and records what it gets back
             return mode
-        # "greedy+pen", "sample+lp", "rows+pen+con+lp", ...: graphs of their own
-        return mode + ("+pen" if pen else "") + ("+con" if con else "") + ("+lp" if lp else "")
+        # "greedy+pen", "sample+lp", "greedy+gr", "rows+pen+con+gr+lp", ...: graphs of their own
+        return mode + ("+pen" if pen else "") + ("+con" if con else "") + ("+gr" if gr else "") + ("+lp" if lp else "")
 
     @property
     def _captured_greedy(self):                                 # kept for the developer tools that read it
@@ -601,7 +647,7 @@ class DecodeSession:
 
     @torch.no_grad()
     def capture(self, greedy: bool = True, sample: bool = False, rows: bool = False, pen: bool = False, lp: bool = False,
-                con: bool = False, beam: bool = False):
+                con: bool = False, beam: bool = False, gr: bool = False):
         """Capture one decode step of the mode - "sample": the device sampler picks the next token, "greedy": the argmax does,
         "rows": the batched generation's per-row kernel does (arm_rows), "logits": the host decides - or keep the captured one while nothing it bakes in has changed.  Graphs of several modes live
         side by side (a decoder that alternates greedy and sampled generations captures each once).  ``pen``: the step with the sampling
@@ -609,12 +655,14 @@ class DecodeSession:
         next to the plain ones, which stay as they are.  ``lp``: the step with the log-prob record's launch (arm_logprobs) behind the
         selection - "greedy+lp", "rows+pen+lp", ... - again graphs of their own.  ``con``: the step with the history constraints' launch
         (arm_constraints) behind the penalties' and in front of the selection - "greedy+con", "rows+pen+con+lp", ... - likewise.
-        ``beam``: the beam search's step (arm_beams) - "beam", captured next to the others."""
+        ``beam``: the beam search's step (arm_beams) - "beam", captured next to the others.  ``gr``: the step with the grammar's launch
+        (arm_grammar) behind the history constraints' and in front of the selection - "greedy+gr", "rows+pen+con+gr+lp", ... - graphs of
+        their own as well; tables and states are device memory, so one graph serves every pattern."""
         if not self.use_graph:
             return
         from . import _lib
-        mode = self._mode(greedy, sample, rows, pen, lp, con, beam)
-        pen, lp, con = "+pen" in mode, mode.endswith("+lp"), "+con" in mode
+        mode = self._mode(greedy, sample, rows, pen, lp, con, beam, gr)
+        pen, lp, con, gr = "+pen" in mode, mode.endswith("+lp"), "+con" in mode, "+gr" in mode
         if beam:
             greedy = sample = rows = False
             if self.beams is None or self.beams.B < 1:
@@ -625,6 +673,8 @@ class DecodeSession:
             raise RuntimeError("capture(con=True) before arm_constraints")
         if lp and self.lp is None:
             raise RuntimeError("capture(lp=True) before arm_logprobs")
+        if gr and self.gr is None:
+            raise RuntimeError("capture(gr=True) before arm_grammar")
         if self._graphs:
             # cheap test first (a process-wide counter every derived-layout build / drop bumps), the full fingerprint when it moved
             valid = self._graph_epoch == _lib.layout_epoch() and self._graph_versions == self._canonical_versions()
@@ -642,10 +692,11 @@ class DecodeSession:
             self.release_prefill_layouts()
         # (the token counts of the sampling controls included: the warm-up runs must not count tokens; and the log-prob record's
         # entry counts: they must record nothing - what they wrote past the count is overwritten by the steps that follow; and the
-        # history constraints' lengths: they must append nothing that survives - a row they stop comes back with row_state / live)
+        # history constraints' lengths: they must append nothing that survives - a row they stop comes back with row_state / live; and
+        # the grammars' states: the warm-up runs must not walk them)
         state = ((self.tok, self.write_index, self.pos, self.mask, self.rng_state) + self.rows.tensors()
                  + (self.pen.tensors() if pen else ()) + ((self.lp.count,) if lp else ()) + (self.con.tensors() if con else ())
-                 + (self.beams.tensors() + (self.beams.first,) if beam else ()))
+                 + (self.gr.tensors() if gr else ()) + (self.beams.tensors() + (self.beams.first,) if beam else ()))
         saved = tuple(t.clone() for t in state)
         if beam:
             # the warm-up's gathers touch only cache positions its own steps write, [write_index now, write_index then): every one of
@@ -654,20 +705,20 @@ class DecodeSession:
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
-            self._step_body(greedy, sample, rows, pen, lp, con, beam)          # warm-up: allocations, lazy repacks
+            self._step_body(greedy, sample, rows, pen, lp, con, beam, gr)          # warm-up: allocations, lazy repacks
             # the warm-up built what the step reads (e.g. the gate-interleaved copy of w_in): what it made redundant goes now,
             # and the step runs once more so that every pre-bound launch exists before the capture
             if self.decode_only and self.release_prefill_layouts():
-                self._step_body(greedy, sample, rows, pen, lp, con, beam)
+                self._step_body(greedy, sample, rows, pen, lp, con, beam, gr)
             if self.low_footprint and self.drop_canonical():
-                self._step_body(greedy, sample, rows, pen, lp, con, beam)      # the pre-bound launches re-validate against the stand-in buffers
+                self._step_body(greedy, sample, rows, pen, lp, con, beam, gr)      # the pre-bound launches re-validate against the stand-in buffers
         torch.cuda.current_stream(self.device).wait_stream(side)
         if self._graphs and self._graph_epoch != _lib.layout_epoch():
             self._graphs.clear()                                # this mode's warm-up rebuilt / dropped a layout the older graphs baked in
             self._graph_logits.clear()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            self._step_body(greedy, sample, rows, pen, lp, con, beam)
+            self._step_body(greedy, sample, rows, pen, lp, con, beam, gr)
         # capture ran the body twice on live state: restore (the cache rows it touched get rewritten)
         for dst, src in zip(state, saved):
             dst.copy_(src)
@@ -705,7 +756,7 @@ class DecodeSession:
 
     @torch.no_grad()
     def decode_step(self, token: Optional[Tensor] = None, greedy: bool = True, sample: bool = False, rows: bool = False,
-                    pen: bool = False, lp: bool = False, con: bool = False, beam: bool = False) -> Tensor:
+                    pen: bool = False, lp: bool = False, con: bool = False, beam: bool = False, gr: bool = False) -> Tensor:
         """Advance by one token.  `token` (batch, 1) overrides the device-resident next id (needed when the
         host samples).  ``sample``: the device sampler (set_sampling) draws the next id into ``tok``.  Returns this step's
         last-position logits (batch, vocab).  ``rows``: the batched generation's step (arm_rows): every row selects, records and
@@ -717,20 +768,22 @@ class DecodeSession:
         (arm_constraints) append the id fed into the step, stop rows (``rows`` only) and ban entries behind the penalties and in
         front of the selection; the host-decides mode leaves that to its caller too (``fused_ops.history_constraints``).  ``beam``:
         the beam search's step (arm_beams): every row's candidates, the cross-beam selection and the cache reorder by parent beam;
-        returns None (the beams are in ``beams``)."""
+        returns None (the beams are in ``beams``).  ``gr``: the armed grammars (arm_grammar) walk the id fed into the step and mask
+        what their automata do not survive, behind the history constraints and in front of the selection; the host-decides mode leaves
+        that to its caller as well (``fused_ops.grammar_mask``)."""
         if self.length + 1 > self.capacity:
             raise ValueError("cache capacity exhausted")
         if token is not None:
             self.tok.copy_(token.to(self.device))
-        mode = self._mode(greedy, sample, rows, pen, lp, con, beam)
-        pen, lp, con = "+pen" in mode, mode.endswith("+lp"), "+con" in mode
+        mode = self._mode(greedy, sample, rows, pen, lp, con, beam, gr)
+        pen, lp, con, gr = "+pen" in mode, mode.endswith("+lp"), "+con" in mode, "+gr" in mode
         if mode in self._graphs:
             from . import _lib
             if self._graph_epoch != _lib.layout_epoch() or self._captured_mode != mode:   # a derived layout was rebuilt / dropped since
-                self.capture(greedy, sample, rows, pen, lp, con, beam)   # the capture: capture() compares the fingerprint and keeps the graphs
+                self.capture(greedy, sample, rows, pen, lp, con, beam, gr)   # the capture: capture() compares the fingerprint and keeps the graphs
             self.graph.replay()                                 # when only modules of OTHER models / sessions moved (ADVICE r3)
         else:
-            self._step_body(greedy, sample, rows, pen, lp, con, beam)
+            self._step_body(greedy, sample, rows, pen, lp, con, beam, gr)
         self.length += 1
         self.cache.length = self.length
         return None if rows or beam else self.logits
@@ -784,7 +837,10 @@ def _existing(p):
 
 class ChatGLMDecoder:
     def __init__(self, config, model: ChatGLM2Model, tokenizer=None, eos_token_id: Optional[int] = None, device=None,
-                 max_sequence_length: Optional[int] = None, time_log: bool = False, low_footprint: bool = False):
+                 max_sequence_length: Optional[int] = None, time_log: bool = False, low_footprint: bool = False, token_bytes=None):
+        # token_bytes (grammar.TokenBytes, or anything grammar.token_byte_table takes): every token's bytes, what ``grammar=`` walks;
+        # None: built from the tokenizer's sentencepiece file by the first generation with a grammar
+        self.token_bytes = token_bytes
         # low_footprint: the decoder's sessions drop the canonical GPU buffers of every int4 module once the derived layouts a phase
         # reads exist (DecodeSession(low_footprint=True): state_dict() / save_pretrained rebuild them byte for byte)
         self.low_footprint = low_footprint
@@ -865,6 +921,26 @@ class ChatGLMDecoder:
             warnings.warn("save_pretrained: no tokenizer file known (pass tokenizer_file=): the folder will hold the model only and the "
                           "reference's load_model_and_tokenizer will not open it")
         save_model(path, self.config, self.model, shard=shard, tokenizer_file=tok)
+
+    def _grammar_table(self):
+        """The vocabulary's byte table a grammar walks: ``token_bytes=`` of the constructor, or built once from the tokenizer."""
+        from .grammar import TokenBytes, token_byte_table
+        if self.token_bytes is None:
+            if self.tokenizer is None:
+                raise ValueError("grammar: the decoder has neither token_bytes= nor a tokenizer to build the vocabulary's byte table from")
+            self.token_bytes = token_byte_table(self.tokenizer)
+        elif not isinstance(self.token_bytes, TokenBytes):
+            self.token_bytes = token_byte_table(self.token_bytes)
+        return self.token_bytes
+
+    def _grammar_result(self, dfa, ids, eos):
+        """``last_stats["grammar_state"]`` of one row: "accepted" - the row ended on the end token and its bytes are a full match -
+        "open" - the budget ran out inside the pattern - or None without a grammar.  Walked on the host over the ids handed out."""
+        if dfa is None:
+            return None
+        ended = bool(ids) and eos is not None and ids[-1] == eos
+        state = dfa.step(0, self._grammar_table().join(ids[:-1] if ended else ids))
+        return "accepted" if ended and dfa.accepting(state) else "open"
 
     def _session_for(self, capacity: int, use_graph: Optional[bool], batch: int = 1) -> DecodeSession:
         """One DecodeSession (cache + captured HIP graph) per batch size is kept and reused while the requested capacity fits and
@@ -962,7 +1038,7 @@ class ChatGLMDecoder:
                      seed: Optional[int] = None, device_sampler: Optional[bool] = None, repetition_penalty: float = 1.0,
                      presence_penalty: float = 0.0, frequency_penalty: float = 0.0, logit_bias: Optional[dict] = None,
                      logprobs: Optional[int] = None, no_repeat_ngram_size: int = 0, bad_words_ids=None, stop_sequences=None,
-                     min_new_tokens: int = 0):
+                     min_new_tokens: int = 0, grammar=None):
         """Yields generated token ids one by one (batch 1, like the reference, chatglm_q/decoder.py:70).
 
         Default = the reference's only mode: top-k / top-p sampling (top_k 100, top_p 0.8, temperature 1.0).  On a GPU the
@@ -994,7 +1070,17 @@ class ChatGLMDecoder:
         ``fused_ops.CONSTRAINT_SEQS_MAX`` sequences of all kinds together, each of at most ``CONSTRAINT_SEQ_LEN_MAX`` ids.  The bans
         run as one more launch inside the captured step, behind the penalties' and in front of the selection, on the ordered history
         kept on the device; stop sequences are matched by the host against the ids it reads anyway.  ``last_stats["constraints"]``
-        says whether any of them was on, ``last_stats["stop_sequence"]`` which stop sequence the output ends with (None: none)."""
+        says whether any of them was on, ``last_stats["stop_sequence"]`` which stop sequence the output ends with (None: none).
+
+        ``grammar`` (None: off, the path above exactly): a ``grammar.ByteDFA`` or a pattern string (``grammar.compile_regex`` lists the
+        syntax) the OUTPUT must match, at the byte level: after every token the concatenation of the generated ids' byte strings
+        (``grammar.TokenBytes.join``; the end token excluded) is a viable prefix of the pattern's language, and the end token can be
+        chosen only when it is a full match.  One more launch inside the captured step, behind the history constraints' and in front of
+        the selection, on the automaton state kept on the device.  It needs an end token id (not ``ignore_eos``) and the vocabulary's
+        byte table (``token_bytes=`` of the constructor, or a tokenizer with a sentencepiece file), and it does not go together with
+        ``min_new_tokens``: the two can leave a row with nothing allowed.  (sentencepiece's ``decode`` drops one leading space of the
+        joined bytes - its dummy prefix.)  ``last_stats["grammar"]`` says whether it was on, ``last_stats["grammar_state"]`` how the
+        output ended: "accepted" (the end token, a full match), "open" (the budget ran out inside the pattern) or None."""
         n_lp = check_logprobs(logprobs)
         self.last_logprobs = None
         prefix = list(prefix_ids)
@@ -1005,6 +1091,15 @@ class ChatGLMDecoder:
                                                                     eos, vocab=self.model.config.vocab_size)
         stops = [q for kind, q in table if kind == fused_ops.ConstraintState.STOP]
         con_settings = [(n_gram, min_new, [e for e in table if e[0] != fused_ops.ConstraintState.STOP])]
+        dfa = tokens = None
+        if grammar is not None:
+            from .grammar import as_dfa
+            dfa = as_dfa(grammar)
+            if eos is None:
+                raise ValueError("grammar needs an end token id (eos_token_id, and not ignore_eos): the end token is how a match ends")
+            if min_new > 0:
+                raise ValueError("grammar and min_new_tokens do not go together: the two can leave a row with nothing allowed")
+            tokens = self._grammar_table()
         limit = min(self.max_sequence_length, self.model.config.max_sequence_length)   # the cache cannot outgrow the rotary table
         budget = min(max_generated_tokens, limit - len(prefix))
         if budget <= 0:
@@ -1017,6 +1112,7 @@ class ChatGLMDecoder:
         try:
             pen = sess.arm_penalties([prefix], repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
             con = sess.arm_constraints([prefix], checked=con_settings)
+            gr = dfa is not None and sess.arm_grammar([dfa], eos, tokens)
             dev_sample = (not greedy) and sess.device_sampler_serves(top_k) and device_sampler is not False
             if device_sampler and not greedy and not dev_sample:
                 raise ValueError(f"device_sampler=True needs a GPU and top_k <= 1024 (got {sess.device}, top_k {top_k})")
@@ -1026,12 +1122,12 @@ class ChatGLMDecoder:
                 sess.set_sampling(top_k, top_p, temperature, seed)
             if n_lp is None:
                 yield from self._generate(sess, prefix, budget, top_k, top_p, temperature, greedy, ignore_eos, prefill_chunk,
-                                          sync_every_token, dev_sample, pen, con=con, stops=stops)
+                                          sync_every_token, dev_sample, pen, con=con, stops=stops, gr=gr, dfa=dfa)
             else:
                 sess.arm_logprobs(True)
                 returned = 0
                 inner = self._generate(sess, prefix, budget, top_k, top_p, temperature, greedy, ignore_eos, prefill_chunk,
-                                       sync_every_token, dev_sample, pen, lp=True, con=con, stops=stops)
+                                       sync_every_token, dev_sample, pen, lp=True, con=con, stops=stops, gr=gr, dfa=dfa)
                 try:
                     for token in inner:
                         returned += 1
@@ -1047,7 +1143,7 @@ class ChatGLMDecoder:
 
     def _generate(self, sess: DecodeSession, prefix, budget: int, top_k: int, top_p: float, temperature: float, greedy: bool,
                   ignore_eos: bool, prefill_chunk: Optional[int], sync_every_token: bool, dev_sample: bool = False, pen: bool = False,
-                  lp: bool = False, con: bool = False, stops=()):
+                  lp: bool = False, con: bool = False, stops=(), gr: bool = False, dfa=None):
         # `auto`: the device picks the next token inside the step (argmax or the one-launch sampler) and feeds it back itself
         auto = greedy or dev_sample
         times = []
@@ -1059,6 +1155,8 @@ class ChatGLMDecoder:
             logits = sess.penalize_first(logits)
         if con:                                                    # ... and the bans the prompt alone decides
             logits = sess.constrain_first(logits)
+        if gr:                                                     # ... and what the pattern's start state does not survive
+            logits = sess.grammar_first(logits)
         if dev_sample:
             nxt = sess.sample_first(logits)
         else:
@@ -1078,7 +1176,7 @@ class ChatGLMDecoder:
         device_loop = auto and not sync_every_token and (ignore_eos or self.eos_token_id is None) and not stops
         if len(generated) < budget and (ignore_eos or token != self.eos_token_id) and not stopped():
             sess.tok.fill_(token)
-            sess.capture(greedy=greedy, sample=dev_sample, pen=pen, lp=lp, con=con)
+            sess.capture(greedy=greedy, sample=dev_sample, pen=pen, lp=lp, con=con, gr=gr)
         pending = []
         # Greedy or device-sampled decoding on a captured step: the graph feeds its own choice back, so step k + 1 does not wait for the HOST to have seen
         # token k.  It is launched before token k is read (one step of speculation: wasted - and harmless, the next prefill re-arms the
@@ -1091,7 +1189,7 @@ class ChatGLMDecoder:
             events = [torch.cuda.Event(), torch.cuda.Event()]
 
             def launch(k):
-                sess.decode_step(None, greedy=greedy, sample=dev_sample, pen=pen, lp=lp, con=con)
+                sess.decode_step(None, greedy=greedy, sample=dev_sample, pen=pen, lp=lp, con=con, gr=gr)
                 ring[k & 1].copy_(sess.tok.view(-1), non_blocking=True)
                 events[k & 1].record()
 
@@ -1116,13 +1214,13 @@ class ChatGLMDecoder:
             t0 = time.perf_counter()
             if device_loop:
                 # the graph feeds its own choice back as the next input: the host only replays
-                sess.decode_step(greedy=greedy, sample=dev_sample, pen=pen, lp=lp, con=con)
+                sess.decode_step(greedy=greedy, sample=dev_sample, pen=pen, lp=lp, con=con, gr=gr)
                 pending.append(sess.tok.clone())
                 generated.append(-1)
                 times.append(time.perf_counter() - t0)
                 continue
             logits = sess.decode_step(None if auto else torch.tensor([[generated[-1]]]), greedy=greedy, sample=dev_sample, pen=pen,
-                                      lp=lp, con=con)
+                                      lp=lp, con=con, gr=gr)
             if pen and not auto:                                   # the host samples: it adjusts the logits it got back (tok = the id just fed)
                 from . import fused_ops
                 logits = fused_ops.logit_penalties(logits if logits.stride(-1) == 1 else logits.contiguous(), sess.pen, sess.tok.view(-1))
@@ -1130,6 +1228,9 @@ class ChatGLMDecoder:
                 from . import fused_ops
                 logits = fused_ops.history_constraints(logits if logits.stride(-1) == 1 else logits.contiguous(), sess.con,
                                                        sess.tok.view(-1))
+            if gr and not auto:                                    # ... and masks them, behind the history constraints
+                from . import fused_ops
+                logits = fused_ops.grammar_mask(logits if logits.stride(-1) == 1 else logits.contiguous(), sess.gr, sess.tok.view(-1))
             nxt = sess.tok[:, 0] if auto else top_p_sampling(logits, top_k, top_p, temperature)
             if lp and not auto:                                    # ... and records its own choice on the logits it sampled from
                 from . import fused_ops
@@ -1154,6 +1255,7 @@ class ChatGLMDecoder:
             "gen_tok_per_s": (n - 1) / rest if n > 1 and rest > 0 else float("nan"),
             "avg_tok_per_s": n / sum(times), "penalties": bool(pen), "logprobs": bool(lp),
             "constraints": bool(con or stops), "stop_sequence": matched_stop_sequence(generated, stops),
+            "grammar": bool(gr), "grammar_state": self._grammar_result(dfa, generated, self.eos_token_id) if gr else None,
         }
         if self.time_log:
             s = self.last_stats
@@ -1187,7 +1289,7 @@ class ChatGLMDecoder:
                            seed=None, ignore_eos: bool = False, prefill_chunk: Optional[int] = None, use_graph: Optional[bool] = None,
                            poll_every: Optional[int] = None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
                            logit_bias=None, logprobs: Optional[int] = None, no_repeat_ngram_size=0, bad_words_ids=None,
-                           stop_sequences=None, min_new_tokens=0):
+                           stop_sequences=None, min_new_tokens=0, grammar=None):
         """Generate for a batch of prompts (lists of token ids, any lengths: LEFT padded with 0 as ``score_ids`` pads them) in one
         decode batch; returns one list of generated ids per prompt.  A row that stopped on the end token ends with it, as
         ``generate_ids`` yields it.
@@ -1221,7 +1323,12 @@ class ChatGLMDecoder:
         every row's own ordered history.  A row that has generated one of its stop sequences is finished ON THE DEVICE by the step
         that follows (one row-step is spent on seeing it) and its ids end with the sequence.  Defaults: off, the path above exactly;
         ``last_stats["constraints"]`` says whether they were active, ``last_stats["stop_sequence"]`` holds, per row, which of its stop
-        sequences its ids end with (None: none)."""
+        sequences its ids end with (None: none).
+
+        ``grammar`` is ``generate_ids``' too: one ``grammar.ByteDFA`` / pattern string for every row, or a list with one per prompt, None
+        for an unconstrained row - every row follows its own automaton in the same launch, and a row without one gets the ids of the
+        same call without ``grammar``.  A row with a grammar needs the end token and must not have ``min_new_tokens``.
+        ``last_stats["grammar"]`` says whether any row had one, ``last_stats["grammar_state"]`` holds "accepted" / "open" / None per row."""
         n_lp = check_logprobs(logprobs)
         self.last_logprobs = None
         prompts = [list(map(int, p)) for p in prompts]
@@ -1268,9 +1375,24 @@ class ChatGLMDecoder:
         con_settings = fused_ops.ConstraintState.check(B, no_repeat_ngram_size, bad_words_ids, stop_sequences, min_new_tokens, stop,
                                                        vocab=self.model.config.vocab_size)
         row_stops = [[q for kind, q in table if kind == fused_ops.ConstraintState.STOP] for _, _, table in con_settings]
+        dfas, tokens = [None] * B, None
+        if grammar is not None:
+            from .grammar import as_dfa
+            compiled = {}                                       # (a pattern given for every row is compiled once)
+            for b, g in enumerate(fused_ops.ConstraintState.per_row("grammar", grammar, B)):
+                if g is not None:
+                    dfas[b] = compiled[id(g)] if id(g) in compiled else compiled.setdefault(id(g), as_dfa(g))
+            for b in range(B):
+                if dfas[b] is not None and stop is None:
+                    raise ValueError("grammar needs an end token id (eos_token_id, and not ignore_eos): the end token is how a match ends")
+                if dfas[b] is not None and con_settings[b][1] > 0:
+                    raise ValueError(f"row {b}: grammar and min_new_tokens do not go together: the two can leave a row with nothing allowed")
+            if any(d is not None for d in dfas):
+                tokens = self._grammar_table()
         if max(budgets) == 0:
             self.last_stats = {"batch": B, "prefix": [len(p) for p in prompts], "generated": [0] * B, "steps": 0, "penalties": False,
-                               "logprobs": n_lp is not None, "constraints": False, "stop_sequence": [None] * B}
+                               "logprobs": n_lp is not None, "constraints": False, "stop_sequence": [None] * B,
+                               "grammar": False, "grammar_state": [None] * B}
             if n_lp is not None:
                 self.last_logprobs = [GenerationLogprobs([], [], []) for _ in prompts]
             return [[] for _ in prompts]
@@ -1286,6 +1408,7 @@ class ChatGLMDecoder:
             sess.arm_rows(list(zip(ks, ps, ts)), seeds, budgets, stop)
             pen = sess.arm_penalties(prompts, *pen_args)
             con = sess.arm_constraints(prompts, checked=con_settings)
+            gr = tokens is not None and sess.arm_grammar(dfas, stop, tokens)
             lp = sess.arm_logprobs(n_lp is not None)
             cuda = sess.device.type == "cuda"
             t0 = time.perf_counter()
@@ -1294,6 +1417,8 @@ class ChatGLMDecoder:
                 logits = sess.penalize_first(logits, rows=True)
             if con:
                 logits = sess.constrain_first(logits, rows=True)
+            if gr:
+                logits = sess.grammar_first(logits, rows=True)
             sess.sample_rows_first(logits)
             if lp:
                 sess.logprobs_first(logits, rows=True)
@@ -1301,7 +1426,7 @@ class ChatGLMDecoder:
             t_first = time.perf_counter() - t0
             steps, max_steps = 0, max(budgets) - 1
             if live > 0 and max_steps > 0:
-                sess.capture(greedy=False, rows=True, pen=pen, lp=lp, con=con)
+                sess.capture(greedy=False, rows=True, pen=pen, lp=lp, con=con, gr=gr)
                 if cuda:
                     ring = torch.zeros((2, 1 + 2 * B), dtype=torch.int32).pin_memory()
                     events = [torch.cuda.Event(), torch.cuda.Event()]
@@ -1309,7 +1434,7 @@ class ChatGLMDecoder:
                 while steps < max_steps:
                     n = min(poll, max_steps - steps)
                     for _ in range(n):
-                        sess.decode_step(greedy=False, rows=True, pen=pen, lp=lp, con=con)
+                        sess.decode_step(greedy=False, rows=True, pen=pen, lp=lp, con=con, gr=gr)
                     steps += n
                     if not cuda:
                         if int(sess.rows.live[0]) == 0:
@@ -1343,6 +1468,7 @@ class ChatGLMDecoder:
             "gen_tok_per_s": (gen - sum(1 for c in counts if c)) / rest if steps and rest > 0 else float("nan"),
             "avg_tok_per_s": gen / total if total > 0 else float("nan"), "penalties": bool(pen), "logprobs": bool(lp),
             "constraints": bool(con), "stop_sequence": [matched_stop_sequence(res[b], row_stops[b]) for b in range(B)],
+            "grammar": bool(gr), "grammar_state": [self._grammar_result(dfas[b], res[b], stop) for b in range(B)],
         }
         if self.time_log:
             s = self.last_stats
@@ -1374,7 +1500,7 @@ class ChatGLMDecoder:
         length.  A prompt still searching when the budget ``min(max_generated_tokens, limit - S)`` runs out (S = the longest prompt,
         limit = the maximum sequence length) adds its running beams as hypotheses.  A budget of 0 returns ``[]`` per prompt.  With
         ``ignore_eos`` (or no end token) nothing finishes early.  ``num_beams=1`` is greedy decoding.  Sampling, penalties, logit bias,
-        log-prob records and history constraints are not part of a beam search."""
+        log-prob records, history constraints and grammars are not part of a beam search."""
         from . import fused_ops
         single = len(prompts) > 0 and not isinstance(prompts[0], (list, tuple))
         prompts = [list(map(int, p)) for p in ([prompts] if single else prompts)]

@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import os
 
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -969,6 +970,186 @@ def history_constraints(logits: Tensor, state: ConstraintState, tok: Tensor | No
                                              state.seq_count.data_ptr(), _lib.ptr(tok), _lib.ptr(row_state), _lib.ptr(live),
                                              _lib.dtype_code(logits.dtype), _lib.stream_ptr(logits.device))
     _lib.check(st, "qlinear_history_constraints")
+    return logits
+
+
+# ---- regex-constrained generation: the mask of a byte-level DFA over the vocabulary (csrc/grammar_mask.hip, chatglm_q_amd/grammar.py) ------
+GRAMMAR_TABLE_MAX = 16384    # entries of one row's transition table (QL_GRAMMAR_TABLE_MAX, include/qlinear_hip.h): n_states * n_classes
+GRAMMAR_STATES_MAX = 4095    # states of one row's automaton (QL_GRAMMAR_STATES_MAX)
+GRAMMAR_CHUNK = 256          # tokens one workgroup of the launch walks (QL_GRAMMAR_CHUNK): the grid is ceil(N / GRAMMAR_CHUNK) x batch
+GRAMMAR_DEAD = 0xFFFF
+
+
+class GrammarState:
+    """Static buffers of ``grammar_mask`` for a batch of rows (a captured step reads and updates them in place).  Per session: the
+    vocabulary's byte table ``tok_off`` (n_tok + 1,) int32 / ``tok_bytes`` uint8 (``grammar.TokenBytes``).  Per row: ``class_of``
+    (batch, 256) uint8, ``table`` (batch, GRAMMAR_TABLE_MAX) uint16 bit patterns (held as int16), ``accept`` (batch, GRAMMAR_STATES_MAX
+    + 1) uint8, ``cfg`` (batch, 2) int32 = n_states (0: the row has no grammar), eos_id (-1: none), ``state`` (batch,) int32 (-1 = dead)
+    and ``ticket`` (batch,) int32.  ``dfas``: what the last ``arm`` armed; ``active``: whether any row has a grammar."""
+
+    def __init__(self, batch: int, token_bytes, device):
+        from .grammar import TokenBytes
+        if batch < 1:
+            raise ValueError(f"GrammarState: batch >= 1 (got {batch})")
+        if not isinstance(token_bytes, TokenBytes):
+            raise ValueError("GrammarState: token_bytes must be a grammar.TokenBytes (grammar.token_byte_table builds one)")
+        self.batch, self.device, self.token_bytes = batch, torch.device(device), token_bytes
+        self.n_tok, self.n_bytes = len(token_bytes), int(token_bytes.bytes.size)
+        self.tok_off = torch.from_numpy(token_bytes.off.copy()).to(device)
+        self.tok_bytes = torch.from_numpy(token_bytes.bytes.copy() if self.n_bytes else np.zeros(1, dtype=np.uint8)).to(device)
+        self.class_of = torch.zeros((batch, 256), dtype=torch.uint8, device=device)
+        self.table = torch.full((batch, GRAMMAR_TABLE_MAX), -1, dtype=torch.int16, device=device)
+        self.accept = torch.zeros((batch, GRAMMAR_STATES_MAX + 1), dtype=torch.uint8, device=device)
+        self.cfg = torch.zeros((batch, 2), dtype=torch.int32, device=device)
+        self.state = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.ticket = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.dfas = [None] * batch
+        self.active = False
+
+    @staticmethod
+    def check(batch: int, dfas, eos_ids, vocab: int | None = None):
+        """Validate one ``ByteDFA`` or None per row (or one for every row) and the end ids (one, one per row, None = none); returns
+        (dfas, eos_ids) as lists, eos -1 for none.  A ValueError names the offending row."""
+        from .grammar import ByteDFA
+        dfas = ConstraintState.per_row("grammar", dfas, batch)
+        eos = ConstraintState.per_row("eos_id", eos_ids, batch)
+        out = []
+        for b in range(batch):
+            d, e = dfas[b], eos[b]
+            if d is not None and not isinstance(d, ByteDFA):
+                raise ValueError(f"grammar: row {b}: a ByteDFA or None (got {type(d).__name__})")
+            if d is not None and (d.n_states > GRAMMAR_STATES_MAX or d.n_states * d.n_classes > GRAMMAR_TABLE_MAX):
+                raise ValueError(f"grammar: row {b}: {d.n_states} states x {d.n_classes} byte classes outside the caps "
+                                 f"({GRAMMAR_STATES_MAX} states, {GRAMMAR_TABLE_MAX} table entries)")
+            if e is None:
+                e = -1
+            if not _is_int(e) or not -1 <= int(e) < (2 ** 31 if vocab is None else vocab):
+                raise ValueError(f"grammar: row {b}: eos_id {e!r} outside the vocabulary")
+            out.append(int(e))
+        return dfas, out
+
+    def arm(self, dfas, eos_ids=None):
+        """Start a generation, in place (the buffers keep their addresses): row b follows ``dfas[b]`` (None: no grammar) from its start
+        state, ``eos_ids[b]`` is the id allowed exactly in an accepting state.  Every state goes to 0, every ticket to 0."""
+        B = self.batch
+        dfas, eos = self.check(B, dfas, eos_ids)
+        class_of = np.zeros((B, 256), dtype=np.uint8)
+        table = np.full((B, GRAMMAR_TABLE_MAX), GRAMMAR_DEAD, dtype=np.uint16)
+        accept = np.zeros((B, GRAMMAR_STATES_MAX + 1), dtype=np.uint8)
+        cfg = np.zeros((B, 2), dtype=np.int32)
+        for b, d in enumerate(dfas):
+            cfg[b, 1] = eos[b]
+            if d is None:
+                continue
+            cfg[b, 0] = d.n_states
+            class_of[b] = d.class_of
+            table[b, :d.n_states * d.n_classes] = d.table.reshape(-1)
+            accept[b, :d.n_states] = d.accept
+        self.class_of.copy_(torch.from_numpy(class_of))
+        self.table.copy_(torch.from_numpy(table.view(np.int16)))
+        self.accept.copy_(torch.from_numpy(accept))
+        self.cfg.copy_(torch.from_numpy(cfg))
+        self.state.zero_()
+        self.ticket.zero_()
+        self.dfas = list(dfas)
+        self.active = any(d is not None for d in dfas)
+        return self
+
+    def states(self):
+        """Every row's current state, read back: a list of ints, -1 = dead."""
+        return self.state.cpu().tolist()
+
+    def tensors(self):
+        """What a step changes and a capture saves and restores (the tickets are back at 0 behind every launch)."""
+        return (self.state,)
+
+
+def _grammar_mask_host(logits: Tensor, state: GrammarState, tok, row_state):
+    """CPU form of qlinear_grammar_mask: rules 0 - 3 of its comment in include/qlinear_hip.h, row by row in Python."""
+    B, N = logits.shape
+    off, data = state.tok_off.numpy(), state.tok_bytes.numpy()
+    n_tok, n_bytes = state.n_tok, state.n_bytes
+
+    def token(i):
+        if not 0 <= i < min(N, n_tok):
+            return b"", True
+        o0, o1 = int(off[i]), int(off[i + 1])
+        if o0 < 0 or o1 < o0 or o1 > n_bytes:
+            return b"", False                                  # corrupt offsets: masked (the fed id: the state dies)
+        return data[o0:o1].tobytes(), True
+
+    for b in range(B):
+        if row_state is not None and int(row_state[b, 1]) & BatchRows.FINISHED:
+            continue
+        ns = _clamp(int(state.cfg[b, 0]), 0, GRAMMAR_STATES_MAX)
+        if ns == 0:
+            continue
+        eos = int(state.cfg[b, 1])
+        cls = state.class_of[b].tolist()
+        nc = max(cls) + 1
+        ns = min(ns, GRAMMAR_TABLE_MAX // nc)
+        tbl = (state.table[b, :ns * nc].numpy().view(np.uint16)).tolist()
+
+        def walk(s, bs):
+            for v in bs:
+                if s < 0:
+                    break
+                t = tbl[s * nc + cls[v]]
+                s = t if t < ns else -1
+            return s
+
+        s = int(state.state[b])
+        s = s if 0 <= s < ns else -1
+        if tok is not None:
+            fed, ok = token(int(tok[b]))
+            s = walk(s, fed) if ok else -1
+        banned = []
+        for i in range(N):
+            if i == eos:
+                if s >= 0 and not int(state.accept[b, s]):
+                    banned.append(i)
+                continue
+            bs, ok = token(i)
+            if s < 0 or not ok or not bs or walk(s, bs) < 0:
+                banned.append(i)
+        if banned:
+            logits[b, torch.tensor(banned, dtype=torch.long)] = float("-inf")
+        state.state[b] = s
+
+
+def grammar_mask(logits: Tensor, state: GrammarState, tok: Tensor | None = None, row_state: Tensor | None = None) -> Tensor:
+    """Apply every row's automaton to `logits` (B, N) IN PLACE - -inf into every id whose bytes the row's state does not survive, and
+    into the end id unless the state is accepting - and advance the state by the id the step was fed, in one launch
+    (``qlinear_grammar_mask``, whose comment in include/qlinear_hip.h holds the rules).  ``tok`` (B,) int64: the ids fed into this step,
+    walked first; None (the first token after a prefill): the state stays.  ``row_state``: a ``BatchRows``' - finished rows are left
+    untouched.  Returns `logits`.  CPU tensors take the host form (Python, the same rules)."""
+    if not isinstance(state, GrammarState):
+        raise ValueError("grammar_mask: state must be a GrammarState")
+    if logits.dim() != 2 or logits.shape[1] < 1 or logits.stride(1) != 1:
+        raise ValueError(f"grammar_mask: logits must be (B, N) with N >= 1 and unit column stride, got {tuple(logits.shape)}")
+    B, N = logits.shape
+    if B != state.batch:
+        raise ValueError(f"grammar_mask: {B} logits rows for a GrammarState of {state.batch}")
+    if B > 1 and logits.stride(0) < N:
+        raise ValueError("grammar_mask: overlapping logits rows")
+    if tok is not None and (tok.dtype != torch.int64 or tok.numel() != B or not tok.is_contiguous()):
+        raise ValueError("grammar_mask: tok must be a contiguous int64 tensor of B elements")
+    if row_state is not None and (row_state.dtype != torch.int32 or tuple(row_state.shape) != (B, 2) or not row_state.is_contiguous()):
+        raise ValueError("grammar_mask: row_state must be a contiguous int32 (B, 2) tensor (BatchRows.row_state)")
+    for t in (state.state, tok, row_state):
+        if t is not None and t.device != logits.device:
+            raise ValueError(f"grammar_mask: logits on {logits.device}, state on {t.device}")
+    if not logits.is_cuda:
+        _grammar_mask_host(logits, state, None if tok is None else tok.view(-1), row_state)
+        return logits
+    lib = _lib.get_lib()
+    with torch.cuda.device(logits.device):
+        st = lib.qlinear_grammar_mask(logits.data_ptr(), B, N, logits.stride(0) if B > 1 else N, state.tok_off.data_ptr(),
+                                      state.tok_bytes.data_ptr(), state.n_tok, state.n_bytes, state.class_of.data_ptr(),
+                                      state.table.data_ptr(), state.accept.data_ptr(), state.cfg.data_ptr(), state.state.data_ptr(),
+                                      state.ticket.data_ptr(), _lib.ptr(tok), _lib.ptr(row_state), _lib.dtype_code(logits.dtype),
+                                      _lib.stream_ptr(logits.device))
+    _lib.check(st, "qlinear_grammar_mask")
     return logits
 
 

@@ -58,7 +58,9 @@ extern "C" {
  * _MIN) added - purely additive; qlinear_logit_penalties and the selection entry points are unchanged.
  * Still 3: qlinear_w4g32_onetile_kc_launches added - purely additive.
  * Still 3: qlinear_beam_advance and qlinear_beam_gather (and the constant QL_BEAMS_MAX) added - purely additive; qlinear_step_logprobs, which
- * supplies their candidates, is unchanged. */
+ * supplies their candidates, is unchanged.
+ * Still 3: qlinear_grammar_mask (and the constants QL_GRAMMAR_TABLE_MAX, QL_GRAMMAR_STATES_MAX, QL_GRAMMAR_CHUNK) added - purely additive;
+ * qlinear_history_constraints and the selection entry points are unchanged, they read the masked logits. */
 #define QLINEAR_ABI_VERSION 3
 
 /* activation dtypes */
@@ -651,6 +653,50 @@ int qlinear_history_constraints(void* logits, int64_t B, int64_t N, int64_t ldl,
                                 const int32_t* prompt_len, const int32_t* cfg, const int32_t* seq_tok, const int32_t* seq_len,
                                 const int32_t* seq_kind, const int32_t* seq_count, const int64_t* tok, int32_t* row_state, int32_t* live,
                                 int dtype, void* stream);
+
+/* Regex-constrained generation: the mask of a byte-level DFA over the vocabulary, one launch between qlinear_history_constraints (or
+ * qlinear_logit_penalties, or lm_head) and the selection entry points - the order is penalties, history, grammar, selection, log-prob
+ * record.  Edits logits (B, N) IN PLACE (row stride ldl, unit column stride).  Everything a row's pattern decides is read from device
+ * memory and the row's automaton state is kept there and advanced by this launch, so ONE captured graph serves every pattern.
+ *   tok_off (n_tok + 1) int32, tok_bytes (n_bytes) uint8: the vocabulary's byte table, shared by all rows - token id's byte string is
+ *     tok_bytes[tok_off[id] : tok_off[id + 1]]; an id >= n_tok has the empty string.  An EMPTY token is never allowed by a grammar.
+ *   class_of (B, 256) uint8: row b's byte classes; n_classes = 1 + the largest entry.
+ *   table (B, QL_GRAMMAR_TABLE_MAX) uint16: row b's transitions, table[s * n_classes + class] = the next state; an entry outside
+ *     [0, n_states) - 0xFFFF by convention - is DEAD.  The start state is 0.
+ *   accept (B, QL_GRAMMAR_STATES_MAX + 1) uint8: nonzero = accepting.
+ *   cfg (B, 2) int32: n_states (<= 0: the row has no grammar; clamped to QL_GRAMMAR_STATES_MAX and to QL_GRAMMAR_TABLE_MAX / n_classes)
+ *     and eos_id (outside [0, N), -1 by convention: none).
+ *   state (B) int32: the row's current state s, a value outside [0, n_states) - -1 by convention - is dead.  ticket (B) int32: 0 between
+ *     launches.
+ *   tok (B) int64, nullable: the id fed into this step, as in qlinear_logit_penalties.  row_state (B, 2) int32, nullable:
+ *     qlinear_batch_sample_advance's.
+ * walk(s, bytes): from a live s follow table[s * n_classes + class_of[byte]] byte by byte; dead at the first DEAD entry; a dead s stays
+ * dead; no bytes: s.  For row b, in this order:
+ *   0. row_state given and the row's finished bit (bit 0 of [b][1]) set, or n_states <= 0: the row is left entirely untouched - nothing
+ *      is read past that, nothing is written.
+ *   1. advance: tok given: s' = walk(s, bytes(tok[b])).  An id outside [0, N) or [0, n_tok), or one with an empty byte string - the
+ *      end token the greedy loop's speculated step is fed - leaves s' = s.  tok null (the first token after a prefill): s' = s.
+ *   2. mask: for every id in [0, N) other than eos_id: logits[b][id] = -inf (in the logits dtype) when bytes(id) is empty or
+ *      walk(s', bytes(id)) is dead.  For eos_id: logits[b][eos_id] = -inf unless s' is live and accepting; a dead s' leaves eos_id
+ *      alone, so such a row ends.  No logit is read; an allowed entry keeps its bits; nothing outside [row, row + N) is touched.
+ *   3. state[b] = s', stored exactly once per launch.
+ * Grid ceil(N / QL_GRAMMAR_CHUNK) x B workgroups; each copies the row's class map and the live part of its table (n_states *
+ * n_classes entries) into LDS, computes s' itself and walks its own QL_GRAMMAR_CHUNK tokens.  No workgroup reads in this launch
+ * anything another workgroup of this launch wrote: every one reads the OLD state[b]; behind its last logit store and an agent-scope
+ * release it draws a ticket (one agent-scope atomic add on ticket[b]); the one that draws the last ticket stores s' and puts the ticket
+ * back to 0.  Nothing spins or waits on another workgroup.  ticket[b] must be 0 when a launch starts.
+ * Every index is clamped: a corrupt table masks too much and never reads out of range - offsets must satisfy 0 <= tok_off[id] <=
+ * tok_off[id + 1] <= n_bytes or the id is masked (the fed id: the state dies).  Bound: one launch; per row 4 (N + 1) bytes of offsets
+ * plus the token bytes, and the DFA copy once per workgroup.
+ * QL_ERR_BAD_DTYPE; QL_ERR_BAD_SHAPE for N < 1, ldl < N, n_tok < 1, n_bytes < 0, one of them >= 2^31 or B > 65535; QL_ERR_NULL_POINTER for
+ * a missing required buffer (tok_bytes may be null when n_bytes == 0); QL_ERR_MISALIGNED for logits not aligned to the element size, a
+ * table not aligned to 16 bytes or an int32 buffer not aligned to 4; B == 0 is QL_OK without a launch. */
+#define QL_GRAMMAR_TABLE_MAX 16384
+#define QL_GRAMMAR_STATES_MAX 4095
+#define QL_GRAMMAR_CHUNK 256
+int qlinear_grammar_mask(void* logits, int64_t B, int64_t N, int64_t ldl, const int32_t* tok_off, const uint8_t* tok_bytes, int64_t n_tok,
+                         int64_t n_bytes, const uint8_t* class_of, const uint16_t* table, const uint8_t* accept, const int32_t* cfg,
+                         int32_t* state, int32_t* ticket, const int64_t* tok, const int32_t* row_state, int dtype, void* stream);
 
 /* Beam search inside the decode step.  P prompts x B beams (1 <= B <= QL_BEAMS_MAX) are R = P * B batch rows; rows g*B .. g*B+B-1 are
  * group g, every row of a group holds the same prompt.  A beam step is the model step's launches plus three: qlinear_step_logprobs on a
