@@ -140,6 +140,7 @@ EXPORTS = {
                                         c_void_p, c_void_p, c_int, c_void_p]),
     "qlinear_history_constraints": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64] + [c_void_p] * 10 + [c_int, c_void_p]),
     "qlinear_grammar_mask": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] * 8 + [c_int, c_void_p]),
+    "qlinear_pda_mask": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] * 10 + [c_int, c_void_p]),
     "qlinear_gptq_block": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_int64, c_int, c_void_p]),
     "qlinear_step_logprobs": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -858,6 +858,23 @@ int qlinear_grammar_mask(void* logits, int64_t B, int64_t N, int64_t ldl, const 
                         row_state, (hipStream_t)stream);
 }
 
+int qlinear_pda_mask(void* logits, int64_t B, int64_t N, int64_t ldl, const int32_t* tok_off, const uint8_t* tok_bytes, int64_t n_tok,
+                     int64_t n_bytes, const uint8_t* class_of, const uint16_t* table, const uint8_t* accept, const int32_t* cfg,
+                     int32_t* state, int32_t* depth, uint8_t* stack, int32_t* ticket, const int64_t* tok, const int32_t* row_state,
+                     int dtype, void* stream) {
+    if (!dtype_ok(dtype)) return QL_ERR_BAD_DTYPE;
+    if (B < 0 || B > 65535 || !fits_i32(N) || ldl < N || n_tok < 1 || !fits_i32(n_tok) || n_bytes < 0 || n_bytes >= ((int64_t)1 << 31))
+        return QL_ERR_BAD_SHAPE;
+    if (B == 0) return QL_OK;
+    if (!logits || !tok_off || !class_of || !table || !accept || !cfg || !state || !depth || !stack || !ticket) return QL_ERR_NULL_POINTER;
+    if (n_bytes > 0 && !tok_bytes) return QL_ERR_NULL_POINTER;
+    if (!aligned(logits, (size_t)esize(dtype)) || !aligned(table, 16) || !aligned(tok_off, 4) || !aligned(cfg, 4) || !aligned(state, 4) ||
+        !aligned(depth, 4) || !aligned(ticket, 4))
+        return QL_ERR_MISALIGNED;
+    return pda_mask(dtype, logits, B, N, ldl, tok_off, tok_bytes, n_tok, n_bytes, class_of, table, accept, cfg, state, depth, stack, ticket,
+                    tok, row_state, (hipStream_t)stream);
+}
+
 int qlinear_gptq_block(const float* W, int64_t n_rows, int64_t ldw, int64_t c0, int64_t bc, const float* hinv_block, int64_t ldh, int bits,
                        int64_t group, float* Q, float* Err, float* Loss, float* scale, int64_t lds, int dtype, void* stream) {
     if (dtype != QL_DTYPE_F32) return QL_ERR_BAD_DTYPE;

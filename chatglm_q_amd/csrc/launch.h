@@ -315,6 +315,11 @@ int grammar_mask(int dtype, void* logits, int64_t B, int64_t N, int64_t ldl, con
                  int64_t n_bytes, const uint8_t* class_of, const uint16_t* table, const uint8_t* accept, const int32_t* cfg, int32_t* state,
                  int32_t* ticket, const int64_t* tok, const int32_t* row_state, hipStream_t st);
 
+// pda_mask.hip: the mask of a byte-level pushdown automaton over the vocabulary in place, the row's state and stack kept on the device
+int pda_mask(int dtype, void* logits, int64_t B, int64_t N, int64_t ldl, const int32_t* tok_off, const uint8_t* tok_bytes, int64_t n_tok,
+             int64_t n_bytes, const uint8_t* class_of, const uint16_t* table, const uint8_t* accept, const int32_t* cfg, int32_t* state,
+             int32_t* depth, uint8_t* stack, int32_t* ticket, const int64_t* tok, const int32_t* row_state, hipStream_t st);
+
 // beam_search.hip: the cross-beam selection with its hypothesis bookkeeping, and the in-place reorder of the key/value cache by parent beam
 int beam_advance(int64_t P, int64_t B, const int32_t* cand_ids, const float* cand_lp, int32_t* cand_count, float* beam_score, int64_t* tok,
                  int32_t* parent, int32_t* trellis, int64_t cap, int32_t* steps, float* fin_score, float* fin_sum, int32_t* fin_len,

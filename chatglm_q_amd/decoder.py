@@ -171,6 +171,10 @@ class DecodeSession:
         # memory, read and advanced by the "+gr" steps.  Allocated by the first generation with a grammar
         self.gr = None
         self._gr_source = None                                  # the TokenBytes the GrammarState was built from
+        # JSON-constrained generation (arm_grammar, when a row's grammar is a grammar.BytePDA): the same with a stack beside every row's
+        # state, read and advanced by the "+pda" steps - which then serve the call's DFA rows too.  Allocated by the first such generation
+        self.pda = None
+        self._pda_source = None
         # beam search (arm_beams): beam scores, parents, the trellis and the finished heaps in device memory, read and updated by the
         # "beam" step, and the table of cache buffers its gather reorders.  Allocated by the first beam search
         self.beams = None
@@ -420,13 +424,17 @@ class DecodeSession:
         Every state starts at 0.  Returns whether any row has a grammar; with none nothing is armed - and nothing allocated - and the
         generation takes the steps without the launch."""
         from . import fused_ops
-        from .grammar import as_dfa
+        from .grammar import BytePDA, as_grammar
         B = self.batch
-        dfas = [None if g is None else as_dfa(g) for g in fused_ops.ConstraintState.per_row("grammar", grammars, B)]
+        dfas = [None if g is None else as_grammar(g) for g in fused_ops.ConstraintState.per_row("grammar", grammars, B)]
+        if self.gr is not None:
+            self.gr.active = False
+        if self.pda is not None:
+            self.pda.active = False
         if all(d is None for d in dfas):
-            if self.gr is not None:
-                self.gr.active = False
             return False
+        if any(isinstance(d, BytePDA) for d in dfas):           # one pushdown row: the whole call takes the "+pda" launch
+            return self._arm_pda(dfas, eos_id, token_bytes)
         dfas, eos = fused_ops.GrammarState.check(B, dfas, eos_id, vocab=self.model.config.vocab_size)
         if token_bytes is None and self.gr is None:
             raise ValueError("arm_grammar: a grammar needs the vocabulary's byte table (token_bytes=, grammar.token_byte_table builds one)")
@@ -443,6 +451,40 @@ class DecodeSession:
             self._gr_source = token_bytes
         self.gr.arm(dfas, eos)
         return True
+
+    def _arm_pda(self, grammars, eos_id, token_bytes) -> bool:
+        """``arm_grammar`` for a call with a ``grammar.BytePDA`` among its rows: every row's grammar goes into ``self.pda``
+        (``fused_ops.PdaState.arm``, a ``ByteDFA`` lifted by ``BytePDA.from_dfa``), ``self.gr`` stays as it is and is not launched."""
+        from . import fused_ops
+        B = self.batch
+        pdas, eos = fused_ops.PdaState.check(B, grammars, eos_id, vocab=self.model.config.vocab_size)
+        if token_bytes is None and self.pda is None:
+            raise ValueError("arm_grammar: a grammar needs the vocabulary's byte table (token_bytes=, grammar.token_byte_table builds one)")
+        if self.pda is None or (token_bytes is not None and token_bytes is not self._pda_source):
+            if self.pda is not None:                            # other buffers: the graphs that baked the old ones in go
+                for mode in [m for m in self._graphs if "+pda" in m]:
+                    self._graphs.pop(mode, None)
+                    self._graph_logits.pop(mode, None)
+                if self._captured_mode is not None and "+pda" in self._captured_mode:
+                    self.graph = self._captured_mode = None
+            vocab = self.model.config.vocab_size
+            table = token_bytes.padded(vocab) if len(token_bytes) < vocab else token_bytes
+            self.pda = fused_ops.PdaState(B, table, self.device)
+            self._pda_source = token_bytes
+        self.pda.arm(pdas, eos)
+        return True
+
+    @property
+    def pda_armed(self) -> bool:
+        """Whether the last ``arm_grammar`` armed the pushdown launch ("+pda") rather than the DFA launch ("+gr")."""
+        return self.pda is not None and self.pda.active
+
+    def pda_first(self, logits: Tensor, rows: bool = False) -> Tensor:
+        """``grammar_first`` of the pushdown launch: the armed automata applied in place to a prefill's last-position logits (nothing
+        generated yet: every configuration stays at its start)."""
+        from . import fused_ops
+        lg = logits if logits.stride(-1) == 1 else logits.contiguous()
+        return fused_ops.pda_mask(lg, self.pda, None, self.rows.row_state if rows else None)
 
     def grammar_first(self, logits: Tensor, rows: bool = False) -> Tensor:
         """The armed grammars applied in place to a prefill's last-position logits (nothing generated yet: every state stays at its
@@ -533,7 +575,7 @@ class DecodeSession:
         fused_ops.batch_sample_advance(logits, self.tok.view(-1), self.rows)
 
     def _step_body(self, greedy: bool, sample: bool = False, rows: bool = False, pen: bool = False, lp: bool = False, con: bool = False,
-                   beam: bool = False, gr: bool = False):
+                   beam: bool = False, gr: bool = False, pda: bool = False):
         # invariant on entry: mask is 0 for positions <= write_index (the new position may attend to itself)
         logits = self.model.step(self.tok, self.cache, self.write_index, self.pos, self.mask, last_only=True)
         if beam:                                                # candidates, cross-beam selection + bookkeeping, cache reorder: three launches
@@ -553,6 +595,9 @@ class DecodeSession:
         if gr and (greedy or sample or rows):                   # walk the id this step was fed, mask what the automaton does not survive:
             from . import fused_ops                             # one launch behind the history constraints', in front of the selection
             fused_ops.grammar_mask(logits[:, -1], self.gr, self.tok.view(-1), self.rows.row_state if rows else None)
+        if pda and (greedy or sample or rows):                  # ... or the pushdown automata's launch in its place: still one launch
+            from . import fused_ops
+            fused_ops.pda_mask(logits[:, -1], self.pda, self.tok.view(-1), self.rows.row_state if rows else None)
         if rows:                                                # per-row selection, recording, stop + the bookkeeping: one launch;
             from . import fused_ops                             # the tokens live in rows.out_tokens (self.logits is not touched)
             fused_ops.batch_sample_advance(logits[:, -1], self.tok.view(-1), self.rows, self.write_index, self.pos.view(-1),
@@ -632,14 +677,14 @@ class DecodeSession:
 
     @staticmethod
     def _mode(greedy: bool, sample: bool, rows: bool = False, pen: bool = False, lp: bool = False, con: bool = False,
-              beam: bool = False, gr: bool = False) -> str:
+              beam: bool = False, gr: bool = False, pda: bool = False) -> str:
         if beam:                                                # the beam search's step: no sampling controls, no record
             return "beam"
         mode = "rows" if rows else ("sample" if sample else ("greedy" if greedy else "logits"))
         if mode == "logits":                                    # the host decides: it adjusts and records what it gets back
             return mode
         # "greedy+pen", "sample+lp", "greedy+gr", "rows+pen+con+gr+lp", ...: graphs of their own
-        return mode + ("+pen" if pen else "") + ("+con" if con else "") + ("+gr" if gr else "") + ("+lp" if lp else "")
+        return mode + ("+pen" if pen else "") + ("+con" if con else "") + ("+gr" if gr else "") + ("+pda" if pda else "") + ("+lp" if lp else "")
 
     @property
     def _captured_greedy(self):                                 # kept for the developer tools that read it
@@ -647,7 +692,7 @@ class DecodeSession:
 
     @torch.no_grad()
     def capture(self, greedy: bool = True, sample: bool = False, rows: bool = False, pen: bool = False, lp: bool = False,
-                con: bool = False, beam: bool = False, gr: bool = False):
+                con: bool = False, beam: bool = False, gr: bool = False, pda: bool = False):
         """Capture one decode step of the mode - "sample": the device sampler picks the next token, "greedy": the argmax does,
         "rows": the batched generation's per-row kernel does (arm_rows), "logits": the host decides - or keep the captured one while nothing it bakes in has changed.  Graphs of several modes live
         side by side (a decoder that alternates greedy and sampled generations captures each once).  ``pen``: the step with the sampling
@@ -657,12 +702,13 @@ class DecodeSession:
         (arm_constraints) behind the penalties' and in front of the selection - "greedy+con", "rows+pen+con+lp", ... - likewise.
         ``beam``: the beam search's step (arm_beams) - "beam", captured next to the others.  ``gr``: the step with the grammar's launch
         (arm_grammar) behind the history constraints' and in front of the selection - "greedy+gr", "rows+pen+con+gr+lp", ... - graphs of
-        their own as well; tables and states are device memory, so one graph serves every pattern."""
+        their own as well; tables and states are device memory, so one graph serves every pattern.  ``pda``: the step with the pushdown
+        automata's launch (arm_grammar with a ``grammar.BytePDA`` among the rows) in the grammar launch's place - "greedy+pda", ..."""
         if not self.use_graph:
             return
         from . import _lib
-        mode = self._mode(greedy, sample, rows, pen, lp, con, beam, gr)
-        pen, lp, con, gr = "+pen" in mode, mode.endswith("+lp"), "+con" in mode, "+gr" in mode
+        mode = self._mode(greedy, sample, rows, pen, lp, con, beam, gr, pda)
+        pen, lp, con, gr, pda = "+pen" in mode, mode.endswith("+lp"), "+con" in mode, "+gr" in mode, "+pda" in mode
         if beam:
             greedy = sample = rows = False
             if self.beams is None or self.beams.B < 1:
@@ -675,6 +721,8 @@ class DecodeSession:
             raise RuntimeError("capture(lp=True) before arm_logprobs")
         if gr and self.gr is None:
             raise RuntimeError("capture(gr=True) before arm_grammar")
+        if pda and self.pda is None:
+            raise RuntimeError("capture(pda=True) before arm_grammar with a BytePDA")
         if self._graphs:
             # cheap test first (a process-wide counter every derived-layout build / drop bumps), the full fingerprint when it moved
             valid = self._graph_epoch == _lib.layout_epoch() and self._graph_versions == self._canonical_versions()
@@ -696,7 +744,7 @@ class DecodeSession:
         # the grammars' states: the warm-up runs must not walk them)
         state = ((self.tok, self.write_index, self.pos, self.mask, self.rng_state) + self.rows.tensors()
                  + (self.pen.tensors() if pen else ()) + ((self.lp.count,) if lp else ()) + (self.con.tensors() if con else ())
-                 + (self.gr.tensors() if gr else ()) + (self.beams.tensors() + (self.beams.first,) if beam else ()))
+                 + (self.gr.tensors() if gr else ()) + (self.pda.tensors() if pda else ()) + (self.beams.tensors() + (self.beams.first,) if beam else ()))
         saved = tuple(t.clone() for t in state)
         if beam:
             # the warm-up's gathers touch only cache positions its own steps write, [write_index now, write_index then): every one of
@@ -705,20 +753,20 @@ class DecodeSession:
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
-            self._step_body(greedy, sample, rows, pen, lp, con, beam, gr)          # warm-up: allocations, lazy repacks
+            self._step_body(greedy, sample, rows, pen, lp, con, beam, gr, pda)          # warm-up: allocations, lazy repacks
             # the warm-up built what the step reads (e.g. the gate-interleaved copy of w_in): what it made redundant goes now,
             # and the step runs once more so that every pre-bound launch exists before the capture
             if self.decode_only and self.release_prefill_layouts():
-                self._step_body(greedy, sample, rows, pen, lp, con, beam, gr)
+                self._step_body(greedy, sample, rows, pen, lp, con, beam, gr, pda)
             if self.low_footprint and self.drop_canonical():
-                self._step_body(greedy, sample, rows, pen, lp, con, beam, gr)      # the pre-bound launches re-validate against the stand-in buffers
+                self._step_body(greedy, sample, rows, pen, lp, con, beam, gr, pda)      # the pre-bound launches re-validate against the stand-in buffers
         torch.cuda.current_stream(self.device).wait_stream(side)
         if self._graphs and self._graph_epoch != _lib.layout_epoch():
             self._graphs.clear()                                # this mode's warm-up rebuilt / dropped a layout the older graphs baked in
             self._graph_logits.clear()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            self._step_body(greedy, sample, rows, pen, lp, con, beam, gr)
+            self._step_body(greedy, sample, rows, pen, lp, con, beam, gr, pda)
         # capture ran the body twice on live state: restore (the cache rows it touched get rewritten)
         for dst, src in zip(state, saved):
             dst.copy_(src)
@@ -756,7 +804,8 @@ class DecodeSession:
 
     @torch.no_grad()
     def decode_step(self, token: Optional[Tensor] = None, greedy: bool = True, sample: bool = False, rows: bool = False,
-                    pen: bool = False, lp: bool = False, con: bool = False, beam: bool = False, gr: bool = False) -> Tensor:
+                    pen: bool = False, lp: bool = False, con: bool = False, beam: bool = False, gr: bool = False,
+                    pda: bool = False) -> Tensor:
         """Advance by one token.  `token` (batch, 1) overrides the device-resident next id (needed when the
         host samples).  ``sample``: the device sampler (set_sampling) draws the next id into ``tok``.  Returns this step's
         last-position logits (batch, vocab).  ``rows``: the batched generation's step (arm_rows): every row selects, records and
@@ -770,20 +819,20 @@ class DecodeSession:
         the beam search's step (arm_beams): every row's candidates, the cross-beam selection and the cache reorder by parent beam;
         returns None (the beams are in ``beams``).  ``gr``: the armed grammars (arm_grammar) walk the id fed into the step and mask
         what their automata do not survive, behind the history constraints and in front of the selection; the host-decides mode leaves
-        that to its caller as well (``fused_ops.grammar_mask``)."""
+        that to its caller as well (``fused_ops.grammar_mask``).  ``pda``: the pushdown automata's launch in that place (``fused_ops.pda_mask``)."""
         if self.length + 1 > self.capacity:
             raise ValueError("cache capacity exhausted")
         if token is not None:
             self.tok.copy_(token.to(self.device))
-        mode = self._mode(greedy, sample, rows, pen, lp, con, beam, gr)
-        pen, lp, con, gr = "+pen" in mode, mode.endswith("+lp"), "+con" in mode, "+gr" in mode
+        mode = self._mode(greedy, sample, rows, pen, lp, con, beam, gr, pda)
+        pen, lp, con, gr, pda = "+pen" in mode, mode.endswith("+lp"), "+con" in mode, "+gr" in mode, "+pda" in mode
         if mode in self._graphs:
             from . import _lib
             if self._graph_epoch != _lib.layout_epoch() or self._captured_mode != mode:   # a derived layout was rebuilt / dropped since
-                self.capture(greedy, sample, rows, pen, lp, con, beam, gr)   # the capture: capture() compares the fingerprint and keeps the graphs
+                self.capture(greedy, sample, rows, pen, lp, con, beam, gr, pda)   # the capture: capture() compares the fingerprint and keeps the graphs
             self.graph.replay()                                 # when only modules of OTHER models / sessions moved (ADVICE r3)
         else:
-            self._step_body(greedy, sample, rows, pen, lp, con, beam, gr)
+            self._step_body(greedy, sample, rows, pen, lp, con, beam, gr, pda)
         self.length += 1
         self.cache.length = self.length
         return None if rows or beam else self.logits
@@ -939,6 +988,12 @@ class ChatGLMDecoder:
         if dfa is None:
             return None
         ended = bool(ids) and eos is not None and ids[-1] == eos
+        from .grammar import PDA_LOCAL_MAX, BytePDA
+        if isinstance(dfa, BytePDA):                            # token by token, as the launch walks it (the window rule is per token)
+            table, config = self._grammar_table(), dfa.start
+            for i in (ids[:-1] if ended else ids):
+                config = dfa.step(config, table.join([i]), window=PDA_LOCAL_MAX)
+            return "accepted" if ended and dfa.accepting(config) else "open"
         state = dfa.step(0, self._grammar_table().join(ids[:-1] if ended else ids))
         return "accepted" if ended and dfa.accepting(state) else "open"
 
@@ -1080,7 +1135,10 @@ class ChatGLMDecoder:
         byte table (``token_bytes=`` of the constructor, or a tokenizer with a sentencepiece file), and it does not go together with
         ``min_new_tokens``: the two can leave a row with nothing allowed.  (sentencepiece's ``decode`` drops one leading space of the
         joined bytes - its dummy prefix.)  ``last_stats["grammar"]`` says whether it was on, ``last_stats["grammar_state"]`` how the
-        output ended: "accepted" (the end token, a full match), "open" (the budget ran out inside the pattern) or None."""
+        output ended: "accepted" (the end token, a full match), "open" (the budget ran out inside the pattern) or None.
+        A ``grammar.BytePDA`` - ``grammar.json_grammar()``: JSON with arbitrary nesting - is taken wherever a ``ByteDFA`` is, under the
+        same preconditions: the step then issues the pushdown automaton's launch (``fused_ops.pda_mask``) in the grammar launch's place,
+        still exactly one launch more than an unconstrained step."""
         n_lp = check_logprobs(logprobs)
         self.last_logprobs = None
         prefix = list(prefix_ids)
@@ -1093,8 +1151,8 @@ class ChatGLMDecoder:
         con_settings = [(n_gram, min_new, [e for e in table if e[0] != fused_ops.ConstraintState.STOP])]
         dfa = tokens = None
         if grammar is not None:
-            from .grammar import as_dfa
-            dfa = as_dfa(grammar)
+            from .grammar import as_grammar
+            dfa = as_grammar(grammar)
             if eos is None:
                 raise ValueError("grammar needs an end token id (eos_token_id, and not ignore_eos): the end token is how a match ends")
             if min_new > 0:
@@ -1113,6 +1171,8 @@ class ChatGLMDecoder:
             pen = sess.arm_penalties([prefix], repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
             con = sess.arm_constraints([prefix], checked=con_settings)
             gr = dfa is not None and sess.arm_grammar([dfa], eos, tokens)
+            pda = gr and sess.pda_armed                            # a BytePDA: the "+pda" launch in the "+gr" launch's place
+            gr = gr and not pda
             dev_sample = (not greedy) and sess.device_sampler_serves(top_k) and device_sampler is not False
             if device_sampler and not greedy and not dev_sample:
                 raise ValueError(f"device_sampler=True needs a GPU and top_k <= 1024 (got {sess.device}, top_k {top_k})")
@@ -1122,12 +1182,12 @@ class ChatGLMDecoder:
                 sess.set_sampling(top_k, top_p, temperature, seed)
             if n_lp is None:
                 yield from self._generate(sess, prefix, budget, top_k, top_p, temperature, greedy, ignore_eos, prefill_chunk,
-                                          sync_every_token, dev_sample, pen, con=con, stops=stops, gr=gr, dfa=dfa)
+                                          sync_every_token, dev_sample, pen, con=con, stops=stops, gr=gr, dfa=dfa, pda=pda)
             else:
                 sess.arm_logprobs(True)
                 returned = 0
                 inner = self._generate(sess, prefix, budget, top_k, top_p, temperature, greedy, ignore_eos, prefill_chunk,
-                                       sync_every_token, dev_sample, pen, lp=True, con=con, stops=stops, gr=gr, dfa=dfa)
+                                       sync_every_token, dev_sample, pen, lp=True, con=con, stops=stops, gr=gr, dfa=dfa, pda=pda)
                 try:
                     for token in inner:
                         returned += 1
@@ -1143,7 +1203,7 @@ class ChatGLMDecoder:
 
     def _generate(self, sess: DecodeSession, prefix, budget: int, top_k: int, top_p: float, temperature: float, greedy: bool,
                   ignore_eos: bool, prefill_chunk: Optional[int], sync_every_token: bool, dev_sample: bool = False, pen: bool = False,
-                  lp: bool = False, con: bool = False, stops=(), gr: bool = False, dfa=None):
+                  lp: bool = False, con: bool = False, stops=(), gr: bool = False, dfa=None, pda: bool = False):
         # `auto`: the device picks the next token inside the step (argmax or the one-launch sampler) and feeds it back itself
         auto = greedy or dev_sample
         times = []
@@ -1157,6 +1217,8 @@ class ChatGLMDecoder:
             logits = sess.constrain_first(logits)
         if gr:                                                     # ... and what the pattern's start state does not survive
             logits = sess.grammar_first(logits)
+        if pda:
+            logits = sess.pda_first(logits)
         if dev_sample:
             nxt = sess.sample_first(logits)
         else:
@@ -1176,7 +1238,7 @@ class ChatGLMDecoder:
         device_loop = auto and not sync_every_token and (ignore_eos or self.eos_token_id is None) and not stops
         if len(generated) < budget and (ignore_eos or token != self.eos_token_id) and not stopped():
             sess.tok.fill_(token)
-            sess.capture(greedy=greedy, sample=dev_sample, pen=pen, lp=lp, con=con, gr=gr)
+            sess.capture(greedy=greedy, sample=dev_sample, pen=pen, lp=lp, con=con, gr=gr, pda=pda)
         pending = []
         # Greedy or device-sampled decoding on a captured step: the graph feeds its own choice back, so step k + 1 does not wait for the HOST to have seen
         # token k.  It is launched before token k is read (one step of speculation: wasted - and harmless, the next prefill re-arms the
@@ -1189,7 +1251,7 @@ class ChatGLMDecoder:
             events = [torch.cuda.Event(), torch.cuda.Event()]
 
             def launch(k):
-                sess.decode_step(None, greedy=greedy, sample=dev_sample, pen=pen, lp=lp, con=con, gr=gr)
+                sess.decode_step(None, greedy=greedy, sample=dev_sample, pen=pen, lp=lp, con=con, gr=gr, pda=pda)
                 ring[k & 1].copy_(sess.tok.view(-1), non_blocking=True)
                 events[k & 1].record()
 
@@ -1214,13 +1276,13 @@ class ChatGLMDecoder:
             t0 = time.perf_counter()
             if device_loop:
                 # the graph feeds its own choice back as the next input: the host only replays
-                sess.decode_step(greedy=greedy, sample=dev_sample, pen=pen, lp=lp, con=con, gr=gr)
+                sess.decode_step(greedy=greedy, sample=dev_sample, pen=pen, lp=lp, con=con, gr=gr, pda=pda)
                 pending.append(sess.tok.clone())
                 generated.append(-1)
                 times.append(time.perf_counter() - t0)
                 continue
             logits = sess.decode_step(None if auto else torch.tensor([[generated[-1]]]), greedy=greedy, sample=dev_sample, pen=pen,
-                                      lp=lp, con=con, gr=gr)
+                                      lp=lp, con=con, gr=gr, pda=pda)
             if pen and not auto:                                   # the host samples: it adjusts the logits it got back (tok = the id just fed)
                 from . import fused_ops
                 logits = fused_ops.logit_penalties(logits if logits.stride(-1) == 1 else logits.contiguous(), sess.pen, sess.tok.view(-1))
@@ -1231,6 +1293,9 @@ class ChatGLMDecoder:
             if gr and not auto:                                    # ... and masks them, behind the history constraints
                 from . import fused_ops
                 logits = fused_ops.grammar_mask(logits if logits.stride(-1) == 1 else logits.contiguous(), sess.gr, sess.tok.view(-1))
+            if pda and not auto:
+                from . import fused_ops
+                logits = fused_ops.pda_mask(logits if logits.stride(-1) == 1 else logits.contiguous(), sess.pda, sess.tok.view(-1))
             nxt = sess.tok[:, 0] if auto else top_p_sampling(logits, top_k, top_p, temperature)
             if lp and not auto:                                    # ... and records its own choice on the logits it sampled from
                 from . import fused_ops
@@ -1255,7 +1320,7 @@ class ChatGLMDecoder:
             "gen_tok_per_s": (n - 1) / rest if n > 1 and rest > 0 else float("nan"),
             "avg_tok_per_s": n / sum(times), "penalties": bool(pen), "logprobs": bool(lp),
             "constraints": bool(con or stops), "stop_sequence": matched_stop_sequence(generated, stops),
-            "grammar": bool(gr), "grammar_state": self._grammar_result(dfa, generated, self.eos_token_id) if gr else None,
+            "grammar": bool(gr or pda), "grammar_state": self._grammar_result(dfa, generated, self.eos_token_id) if gr or pda else None,
         }
         if self.time_log:
             s = self.last_stats
@@ -1377,11 +1442,11 @@ class ChatGLMDecoder:
         row_stops = [[q for kind, q in table if kind == fused_ops.ConstraintState.STOP] for _, _, table in con_settings]
         dfas, tokens = [None] * B, None
         if grammar is not None:
-            from .grammar import as_dfa
+            from .grammar import as_grammar
             compiled = {}                                       # (a pattern given for every row is compiled once)
             for b, g in enumerate(fused_ops.ConstraintState.per_row("grammar", grammar, B)):
                 if g is not None:
-                    dfas[b] = compiled[id(g)] if id(g) in compiled else compiled.setdefault(id(g), as_dfa(g))
+                    dfas[b] = compiled[id(g)] if id(g) in compiled else compiled.setdefault(id(g), as_grammar(g))
             for b in range(B):
                 if dfas[b] is not None and stop is None:
                     raise ValueError("grammar needs an end token id (eos_token_id, and not ignore_eos): the end token is how a match ends")
@@ -1409,6 +1474,8 @@ class ChatGLMDecoder:
             pen = sess.arm_penalties(prompts, *pen_args)
             con = sess.arm_constraints(prompts, checked=con_settings)
             gr = tokens is not None and sess.arm_grammar(dfas, stop, tokens)
+            pda = gr and sess.pda_armed
+            gr = gr and not pda
             lp = sess.arm_logprobs(n_lp is not None)
             cuda = sess.device.type == "cuda"
             t0 = time.perf_counter()
@@ -1419,6 +1486,8 @@ class ChatGLMDecoder:
                 logits = sess.constrain_first(logits, rows=True)
             if gr:
                 logits = sess.grammar_first(logits, rows=True)
+            if pda:
+                logits = sess.pda_first(logits, rows=True)
             sess.sample_rows_first(logits)
             if lp:
                 sess.logprobs_first(logits, rows=True)
@@ -1426,7 +1495,7 @@ class ChatGLMDecoder:
             t_first = time.perf_counter() - t0
             steps, max_steps = 0, max(budgets) - 1
             if live > 0 and max_steps > 0:
-                sess.capture(greedy=False, rows=True, pen=pen, lp=lp, con=con, gr=gr)
+                sess.capture(greedy=False, rows=True, pen=pen, lp=lp, con=con, gr=gr, pda=pda)
                 if cuda:
                     ring = torch.zeros((2, 1 + 2 * B), dtype=torch.int32).pin_memory()
                     events = [torch.cuda.Event(), torch.cuda.Event()]
@@ -1434,7 +1503,7 @@ class ChatGLMDecoder:
                 while steps < max_steps:
                     n = min(poll, max_steps - steps)
                     for _ in range(n):
-                        sess.decode_step(greedy=False, rows=True, pen=pen, lp=lp, con=con, gr=gr)
+                        sess.decode_step(greedy=False, rows=True, pen=pen, lp=lp, con=con, gr=gr, pda=pda)
                     steps += n
                     if not cuda:
                         if int(sess.rows.live[0]) == 0:
@@ -1468,7 +1537,7 @@ class ChatGLMDecoder:
             "gen_tok_per_s": (gen - sum(1 for c in counts if c)) / rest if steps and rest > 0 else float("nan"),
             "avg_tok_per_s": gen / total if total > 0 else float("nan"), "penalties": bool(pen), "logprobs": bool(lp),
             "constraints": bool(con), "stop_sequence": [matched_stop_sequence(res[b], row_stops[b]) for b in range(B)],
-            "grammar": bool(gr), "grammar_state": [self._grammar_result(dfas[b], res[b], stop) for b in range(B)],
+            "grammar": bool(gr or pda), "grammar_state": [self._grammar_result(dfas[b], res[b], stop) for b in range(B)],
         }
         if self.time_log:
             s = self.last_stats

@@ -1153,6 +1153,230 @@ def grammar_mask(logits: Tensor, state: GrammarState, tok: Tensor | None = None,
     return logits
 
 
+# ---- JSON-constrained generation: the mask of a byte-level pushdown automaton over the vocabulary (csrc/pda_mask.hip, grammar.BytePDA) ------
+PDA_DEPTH_MAX = 64           # symbols one row's stack holds (QL_PDA_DEPTH_MAX, include/qlinear_hip.h)
+PDA_LOCAL_MAX = 32           # symbols one token's walk may hold above the lowest depth it reached (QL_PDA_LOCAL_MAX): the window rule
+PDA_SYMS_MAX = 3             # stack symbols 1..n_syms (QL_PDA_SYMS_MAX)
+
+
+class PdaState:
+    """Static buffers of ``pda_mask`` for a batch of rows (a captured step reads and updates them in place).  The vocabulary's byte table
+    and ``class_of`` / ``table`` / ``accept`` / ``ticket`` are ``GrammarState``'s (the table indexed ``(state * (n_syms + 1) + top) *
+    n_classes + class``, entries as ``grammar.pda_entry`` packs them).  Per row besides: ``cfg`` (batch, 4) int32 = n_states (0: the row
+    has no grammar), eos_id (-1: none), n_syms, max_depth; ``state`` (batch,) int32 (-1 = dead); ``depth`` (batch,) int32; ``stack``
+    (batch, PDA_DEPTH_MAX) uint8, bottom first.  ``pdas``: what the last ``arm`` armed; ``active``: whether any row has a grammar."""
+
+    def __init__(self, batch: int, token_bytes, device):
+        from .grammar import TokenBytes
+        if batch < 1:
+            raise ValueError(f"PdaState: batch >= 1 (got {batch})")
+        if not isinstance(token_bytes, TokenBytes):
+            raise ValueError("PdaState: token_bytes must be a grammar.TokenBytes (grammar.token_byte_table builds one)")
+        self.batch, self.device, self.token_bytes = batch, torch.device(device), token_bytes
+        self.n_tok, self.n_bytes = len(token_bytes), int(token_bytes.bytes.size)
+        self.tok_off = torch.from_numpy(token_bytes.off.copy()).to(device)
+        self.tok_bytes = torch.from_numpy(token_bytes.bytes.copy() if self.n_bytes else np.zeros(1, dtype=np.uint8)).to(device)
+        self.class_of = torch.zeros((batch, 256), dtype=torch.uint8, device=device)
+        self.table = torch.full((batch, GRAMMAR_TABLE_MAX), -1, dtype=torch.int16, device=device)
+        self.accept = torch.zeros((batch, GRAMMAR_STATES_MAX + 1), dtype=torch.uint8, device=device)
+        self.cfg = torch.zeros((batch, 4), dtype=torch.int32, device=device)
+        self.state = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.depth = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.stack = torch.zeros((batch, PDA_DEPTH_MAX), dtype=torch.uint8, device=device)
+        self.ticket = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.pdas = [None] * batch
+        self.active = False
+
+    @staticmethod
+    def check(batch: int, pdas, eos_ids, vocab: int | None = None):
+        """Validate one ``BytePDA`` / ``ByteDFA`` (lifted: ``BytePDA.from_dfa``) or None per row (or one for every row) and the end ids
+        (one, one per row, None = none); returns (pdas, eos_ids) as lists, eos -1 for none.  A ValueError names the offending row."""
+        from .grammar import ByteDFA, BytePDA
+        pdas = ConstraintState.per_row("grammar", pdas, batch)
+        eos = ConstraintState.per_row("eos_id", eos_ids, batch)
+        out_p, out_e, lifted = [], [], {}
+        for b in range(batch):
+            d, e = pdas[b], eos[b]
+            if isinstance(d, ByteDFA):
+                d = lifted[id(d)] if id(d) in lifted else lifted.setdefault(id(d), BytePDA.from_dfa(d))
+            if d is not None and not isinstance(d, BytePDA):
+                raise ValueError(f"grammar: row {b}: a BytePDA, a ByteDFA or None (got {type(d).__name__})")
+            if d is not None and (d.n_states > GRAMMAR_STATES_MAX or d.n_states * (d.n_syms + 1) * d.n_classes > GRAMMAR_TABLE_MAX
+                                  or d.n_syms > PDA_SYMS_MAX or d.max_depth > PDA_DEPTH_MAX):
+                raise ValueError(f"grammar: row {b}: {d.n_states} states x {d.n_syms + 1} stack tops x {d.n_classes} byte classes, depth "
+                                 f"{d.max_depth} outside the caps ({GRAMMAR_STATES_MAX} states, {GRAMMAR_TABLE_MAX} table entries, "
+                                 f"{PDA_SYMS_MAX} symbols, depth {PDA_DEPTH_MAX})")
+            if e is None:
+                e = -1
+            if not _is_int(e) or not -1 <= int(e) < (2 ** 31 if vocab is None else vocab):
+                raise ValueError(f"grammar: row {b}: eos_id {e!r} outside the vocabulary")
+            out_p.append(d)
+            out_e.append(int(e))
+        return out_p, out_e
+
+    def arm(self, pdas, eos_ids=None):
+        """Start a generation, in place (the buffers keep their addresses): row b follows ``pdas[b]`` (None: no grammar) from its start
+        configuration - state 0, an empty stack - and ``eos_ids[b]`` is the id allowed exactly in an accepting state with an empty
+        stack.  Every ticket goes to 0."""
+        B = self.batch
+        pdas, eos = self.check(B, pdas, eos_ids)
+        class_of = np.zeros((B, 256), dtype=np.uint8)
+        table = np.full((B, GRAMMAR_TABLE_MAX), GRAMMAR_DEAD, dtype=np.uint16)
+        accept = np.zeros((B, GRAMMAR_STATES_MAX + 1), dtype=np.uint8)
+        cfg = np.zeros((B, 4), dtype=np.int32)
+        for b, d in enumerate(pdas):
+            cfg[b, 1] = eos[b]
+            if d is None:
+                continue
+            cfg[b, 0], cfg[b, 2], cfg[b, 3] = d.n_states, d.n_syms, d.max_depth
+            class_of[b] = d.class_of
+            table[b, :d.table.size] = d.table.reshape(-1)
+            accept[b, :d.n_states] = d.accept
+        self.class_of.copy_(torch.from_numpy(class_of))
+        self.table.copy_(torch.from_numpy(table.view(np.int16)))
+        self.accept.copy_(torch.from_numpy(accept))
+        self.cfg.copy_(torch.from_numpy(cfg))
+        self.state.zero_()
+        self.depth.zero_()
+        self.stack.zero_()
+        self.ticket.zero_()
+        self.pdas = list(pdas)
+        self.active = any(d is not None for d in pdas)
+        return self
+
+    def states(self):
+        """Every row's current state, read back: a list of ints, -1 = dead."""
+        return self.state.cpu().tolist()
+
+    def configs(self):
+        """Every row's configuration, read back: (state, tuple of symbols), or None for a dead row."""
+        s, d, k = self.state.cpu().tolist(), self.depth.cpu().tolist(), self.stack.cpu().tolist()
+        return [None if s[b] < 0 else (s[b], tuple(k[b][:d[b]])) for b in range(self.batch)]
+
+    def tensors(self):
+        """What a step changes and a capture saves and restores (the tickets are back at 0 behind every launch)."""
+        return (self.state, self.depth, self.stack)
+
+
+def _pda_mask_host(logits: Tensor, state: PdaState, tok, row_state):
+    """CPU form of qlinear_pda_mask: rules 0 - 6 of its comment in include/qlinear_hip.h, row by row in Python."""
+    B, N = logits.shape
+    off, data = state.tok_off.numpy(), state.tok_bytes.numpy()
+    n_tok, n_bytes = state.n_tok, state.n_bytes
+
+    def token(i):
+        if not 0 <= i < min(N, n_tok):
+            return b"", True
+        o0, o1 = int(off[i]), int(off[i + 1])
+        if o0 < 0 or o1 < o0 or o1 > n_bytes:
+            return b"", False                                  # corrupt offsets: masked (the fed id: the row dies)
+        return data[o0:o1].tobytes(), True
+
+    for b in range(B):
+        if row_state is not None and int(row_state[b, 1]) & BatchRows.FINISHED:
+            continue
+        ns = min(int(state.cfg[b, 0]), GRAMMAR_STATES_MAX)
+        if ns <= 0:
+            continue
+        eos = int(state.cfg[b, 1])
+        nsy, maxd = _clamp(int(state.cfg[b, 2]), 0, PDA_SYMS_MAX), _clamp(int(state.cfg[b, 3]), 0, PDA_DEPTH_MAX)
+        cls = state.class_of[b].tolist()
+        nc = max(cls) + 1
+        ns = min(ns, GRAMMAR_TABLE_MAX // ((nsy + 1) * nc))
+        tbl = (state.table[b, :ns * (nsy + 1) * nc].numpy().view(np.uint16)).tolist()
+        old = state.stack[b].tolist()
+
+        def walk(s, low, stack, bs):
+            """(s, low, own) behind ``bs`` from state s over stack[:low] (never changed) and no pushes of the walk's own; s = -1: dead."""
+            own = []
+            for v in bs:
+                top = own[-1] if own else (stack[low - 1] if low else 0)
+                e = tbl[(s * (nsy + 1) + top) * nc + cls[v]]
+                t, op, sym = e & 0xFFF, (e >> 12) & 3, e >> 14
+                if t >= ns or op == 3:
+                    return -1, low, own
+                if op == 2:
+                    if sym == 0 or sym > nsy or low + len(own) >= maxd or len(own) >= PDA_LOCAL_MAX:
+                        return -1, low, own
+                    own.append(sym)
+                elif op == 1:
+                    if own:
+                        own.pop()
+                    elif low:
+                        low -= 1
+                    else:
+                        return -1, low, own
+                    if not own and low and not 1 <= stack[low - 1] <= nsy:
+                        return -1, low, own
+                s = t
+            return s, low, own
+
+        s, d = int(state.state[b]), int(state.depth[b])
+        if not 0 <= s < ns or not 0 <= d <= maxd or (d > 0 and not 1 <= old[d - 1] <= nsy):
+            s, d = -1, 0
+        low, own = d, []
+        if tok is not None and s >= 0:
+            fed, ok = token(int(tok[b]))
+            if not ok:
+                s = -1
+            elif fed:
+                s, low, own = walk(s, d, old, fed)
+        new = old[:low] + own if s >= 0 else old
+        d = low + len(own) if s >= 0 else 0
+        banned = []
+        for i in range(N):
+            if i == eos:
+                if s >= 0 and not (int(state.accept[b, s]) and d == 0):
+                    banned.append(i)
+                continue
+            bs, ok = token(i)
+            if s < 0 or not ok or not bs or walk(s, d, new, bs)[0] < 0:
+                banned.append(i)
+        if banned:
+            logits[b, torch.tensor(banned, dtype=torch.long)] = float("-inf")
+        state.state[b] = s
+        if s >= 0:
+            state.depth[b] = d
+            if own:
+                state.stack[b, low:d] = torch.tensor(own, dtype=torch.uint8)
+
+
+def pda_mask(logits: Tensor, state: PdaState, tok: Tensor | None = None, row_state: Tensor | None = None) -> Tensor:
+    """Apply every row's pushdown automaton to `logits` (B, N) IN PLACE - -inf into every id whose bytes the row's configuration does
+    not survive, and into the end id unless the state is accepting and the stack empty - and advance the configuration by the id the
+    step was fed, in one launch (``qlinear_pda_mask``, whose comment in include/qlinear_hip.h holds the rules).  ``tok`` (B,) int64: the
+    ids fed into this step, walked first; None (the first token after a prefill): nothing moves.  ``row_state``: a ``BatchRows``' -
+    finished rows are left untouched.  Returns `logits`.  CPU tensors take the host form (Python, the same rules)."""
+    if not isinstance(state, PdaState):
+        raise ValueError("pda_mask: state must be a PdaState")
+    if logits.dim() != 2 or logits.shape[1] < 1 or logits.stride(1) != 1:
+        raise ValueError(f"pda_mask: logits must be (B, N) with N >= 1 and unit column stride, got {tuple(logits.shape)}")
+    B, N = logits.shape
+    if B != state.batch:
+        raise ValueError(f"pda_mask: {B} logits rows for a PdaState of {state.batch}")
+    if B > 1 and logits.stride(0) < N:
+        raise ValueError("pda_mask: overlapping logits rows")
+    if tok is not None and (tok.dtype != torch.int64 or tok.numel() != B or not tok.is_contiguous()):
+        raise ValueError("pda_mask: tok must be a contiguous int64 tensor of B elements")
+    if row_state is not None and (row_state.dtype != torch.int32 or tuple(row_state.shape) != (B, 2) or not row_state.is_contiguous()):
+        raise ValueError("pda_mask: row_state must be a contiguous int32 (B, 2) tensor (BatchRows.row_state)")
+    for t in (state.state, tok, row_state):
+        if t is not None and t.device != logits.device:
+            raise ValueError(f"pda_mask: logits on {logits.device}, state on {t.device}")
+    if not logits.is_cuda:
+        _pda_mask_host(logits, state, None if tok is None else tok.view(-1), row_state)
+        return logits
+    lib = _lib.get_lib()
+    with torch.cuda.device(logits.device):
+        st = lib.qlinear_pda_mask(logits.data_ptr(), B, N, logits.stride(0) if B > 1 else N, state.tok_off.data_ptr(),
+                                  state.tok_bytes.data_ptr(), state.n_tok, state.n_bytes, state.class_of.data_ptr(),
+                                  state.table.data_ptr(), state.accept.data_ptr(), state.cfg.data_ptr(), state.state.data_ptr(),
+                                  state.depth.data_ptr(), state.stack.data_ptr(), state.ticket.data_ptr(), _lib.ptr(tok),
+                                  _lib.ptr(row_state), _lib.dtype_code(logits.dtype), _lib.stream_ptr(logits.device))
+    _lib.check(st, "qlinear_pda_mask")
+    return logits
+
+
 # ---- log-probabilities during generation: the chosen token's and the most likely alternatives' (csrc/logprob.hip) -------------------------
 TOP_LOGPROBS_MAX = 20        # alternatives one step can record (QL_TOP_LOGPROBS_MAX, include/qlinear_hip.h)
 

@@ -19,7 +19,12 @@ flags, lazy and possessive quantifiers, anchors inside the pattern, ``\\b`` and 
 Pipeline: parser (this module's own) -> Thompson NFA over bytes -> subset construction -> trimming (every kept state reaches an accepting
 state: a live state can always finish) -> minimisation (Hopcroft) -> byte classes (bytes no state distinguishes share a column).
 
-Limits, those of the kernel's LDS copy of the table: ``n_states * n_classes <= GRAMMAR_TABLE_MAX`` and ``n_states <= GRAMMAR_STATES_MAX``."""
+Limits, those of the kernel's LDS copy of the table: ``n_states * n_classes <= GRAMMAR_TABLE_MAX`` and ``n_states <= GRAMMAR_STATES_MAX``.
+
+Past regular languages: ``BytePDA`` is a deterministic real-time pushdown automaton over bytes - one move per byte, no empty moves, one
+bounded stack of at most three symbols - walked by ``fused_ops.pda_mask`` (csrc/pda_mask.hip); ``json_grammar`` builds the one for RFC
+8259 JSON with arbitrary nesting (depth comes from the stack, not from the table), ``BytePDA.from_dfa`` lifts a ``ByteDFA`` (no stack
+symbols, the same language), ``as_grammar`` takes a pattern string, a ``ByteDFA`` or a ``BytePDA``."""
 from collections import deque
 
 import numpy as np
@@ -28,6 +33,11 @@ GRAMMAR_TABLE_MAX = 16384     # entries of one row's transition table (uint16: 3
 GRAMMAR_STATES_MAX = 4095
 DEAD = 0xFFFF                 # table entry: no transition
 REPEAT_MAX = 4096             # the largest count in {m,n}: a bound is unrolled
+PDA_DEPTH_MAX = 64            # symbols a row's stack holds (QL_PDA_DEPTH_MAX)
+PDA_LOCAL_MAX = 32            # symbols ONE token's walk may hold above the lowest depth it reached (QL_PDA_LOCAL_MAX): the window rule
+PDA_SYMS_MAX = 3              # stack symbols 1..n_syms (QL_PDA_SYMS_MAX); 0 = the empty stack read as top
+PDA_DEAD = 0xFFFF             # BytePDA table entry: no move (next state 0xFFF, op 3)
+PDA_NONE, PDA_POP, PDA_PUSH = 0, 1, 2
 
 _ALL = (1 << 256) - 1
 _ASCII = (1 << 128) - 1
@@ -572,6 +582,260 @@ def as_dfa(grammar) -> ByteDFA:
     if isinstance(grammar, str):
         return compile_regex(grammar)
     raise ValueError(f"grammar: a ByteDFA or a pattern string (got {type(grammar).__name__})")
+
+
+def pda_entry(nxt: int, op: int = PDA_NONE, sym: int = 0) -> int:
+    """One ``BytePDA`` table entry: bits 0 - 11 the next state, bits 12 - 13 the op (0 none, 1 pop, 2 push, 3 dead), bits 14 - 15 the
+    pushed symbol."""
+    return (nxt & 0xFFF) | (op & 3) << 12 | (sym & 3) << 14
+
+
+class BytePDA:
+    """A deterministic real-time pushdown automaton over bytes: one move per byte, no empty moves, one stack of symbols 1..``n_syms``
+    (``n_syms`` in 0..PDA_SYMS_MAX) that holds at most ``max_depth`` (<= PDA_DEPTH_MAX) of them.  ``class_of`` (256,) uint8: a byte's
+    column; ``table`` (n_states, n_syms + 1, n_classes) uint16, flat index ``((state * (n_syms + 1) + top) * n_classes + class)`` where
+    ``top`` is 0 for an empty stack and otherwise the symbol on top; ``accept`` (n_states,) uint8 flags.  An entry (``pda_entry``): bits
+    0 - 11 the next state (0xFFF and anything >= n_states: dead), bits 12 - 13 the op (0 none, 1 pop, 2 push, 3 dead), bits 14 - 15 the
+    pushed symbol.  A pop of an empty stack is dead, a push of symbol 0 or of one above ``n_syms`` is dead, a push onto a stack of
+    ``max_depth`` symbols is dead.  The start configuration is state 0 with an empty stack; a configuration accepts when its state is
+    accepting AND its stack is empty.  A configuration is ``(state, tuple of symbols, bottom first)``, or None = dead."""
+
+    start = (0, ())
+
+    def __init__(self, class_of, table, accept, n_syms: int, max_depth: int, name=None):
+        self.n_syms, self.max_depth, self.name = int(n_syms), int(max_depth), name
+        if not 0 <= self.n_syms <= PDA_SYMS_MAX:
+            raise ValueError(f"BytePDA: n_syms {n_syms} outside 0..{PDA_SYMS_MAX} (PDA_SYMS_MAX)")
+        if not 0 <= self.max_depth <= PDA_DEPTH_MAX:
+            raise ValueError(f"BytePDA: max_depth {max_depth} outside 0..{PDA_DEPTH_MAX} (PDA_DEPTH_MAX)")
+        self.class_of = np.ascontiguousarray(class_of, dtype=np.uint8)
+        self.table = np.ascontiguousarray(table, dtype=np.uint16)
+        self.accept = np.ascontiguousarray(accept, dtype=np.uint8)
+        if self.table.ndim != 3 or self.table.shape[1] != self.n_syms + 1 or self.table.shape[0] < 1 or self.table.shape[2] < 1:
+            raise ValueError("BytePDA: table (n_states, n_syms + 1, n_classes)")
+        self.n_states, _, self.n_classes = self.table.shape
+        if self.class_of.shape != (256,) or self.accept.shape != (self.n_states,):
+            raise ValueError("BytePDA: class_of (256,), accept (n_states,)")
+        if int(self.class_of.max()) >= self.n_classes:
+            raise ValueError("BytePDA: class_of names a column the table does not have")
+        entries = self.n_states * (self.n_syms + 1) * self.n_classes
+        if self.n_states > GRAMMAR_STATES_MAX or entries > GRAMMAR_TABLE_MAX:
+            raise ValueError(f"grammar too large: {self.n_states} states x {self.n_syms + 1} stack tops x {self.n_classes} byte classes = "
+                             f"{entries} table entries (at most {GRAMMAR_TABLE_MAX} entries, GRAMMAR_TABLE_MAX, and {GRAMMAR_STATES_MAX} "
+                             f"states, GRAMMAR_STATES_MAX)")
+        self._flat = self.table.reshape(-1).tolist()
+        self._cls = self.class_of.tolist()
+
+    def step(self, config, b: bytes, window=None):
+        """The configuration after ``b`` from ``config``; None = dead (and dead stays dead).  ``window`` (the kernel walks one token with
+        PDA_LOCAL_MAX): dead as soon as the walk holds more than that many symbols above the lowest depth it has reached."""
+        if config is None:
+            return None
+        s, stack = int(config[0]), list(config[1])
+        if not 0 <= s < self.n_states or len(stack) > self.max_depth or any(not 1 <= y <= self.n_syms for y in stack):
+            return None
+        low = len(stack)
+        for v in bytes(b):
+            top = stack[-1] if stack else 0
+            e = self._flat[(s * (self.n_syms + 1) + top) * self.n_classes + self._cls[v]]
+            nxt, op, sym = e & 0xFFF, (e >> 12) & 3, e >> 14
+            if nxt >= self.n_states or op == 3:
+                return None
+            if op == PDA_POP:
+                if not stack:
+                    return None
+                stack.pop()
+                low = min(low, len(stack))
+            elif op == PDA_PUSH:
+                if sym == 0 or sym > self.n_syms or len(stack) == self.max_depth:
+                    return None
+                stack.append(sym)
+                if window is not None and len(stack) - low > window:
+                    return None
+            s = nxt
+        return s, tuple(stack)
+
+    def matches(self, b: bytes) -> bool:
+        return self.accepting(self.step(self.start, b))
+
+    def accepting(self, config) -> bool:
+        return config is not None and 0 <= int(config[0]) < self.n_states and bool(self.accept[int(config[0])]) and len(config[1]) == 0
+
+    @staticmethod
+    def from_dfa(dfa: "ByteDFA") -> "BytePDA":
+        """``dfa`` as a pushdown automaton without stack symbols: the same states, the same language."""
+        if not isinstance(dfa, ByteDFA):
+            raise ValueError(f"BytePDA.from_dfa: a ByteDFA (got {type(dfa).__name__})")
+        t = dfa.table.astype(np.uint16)                          # (a state is at most 4 094: bits 12 - 15 are 0 = no op)
+        t = np.where(t == DEAD, np.uint16(PDA_DEAD), t).reshape(dfa.n_states, 1, dfa.n_classes)
+        return BytePDA(dfa.class_of, t, dfa.accept, 0, 0, name=dfa.pattern)
+
+    def __repr__(self):
+        return (f"BytePDA({self.n_states} states x {self.n_syms + 1} stack tops x {self.n_classes} byte classes, depth <= {self.max_depth}"
+                + (f", {self.name!r})" if self.name is not None else ")"))
+
+
+_HEX = _mask((0x30, 0x39), (0x41, 0x46), (0x61, 0x66))
+_WS = _mask(0x20, 0x09, 0x0A, 0x0D)
+_SYM_ARRAY, _SYM_OBJECT = 1, 2
+
+
+def json_grammar(root: str = "value", whitespace: bool = False, max_depth: int = 16) -> BytePDA:
+    """The ``BytePDA`` of RFC 8259 JSON, built by hand.  ``root``: "value" (any JSON text), "object" or "array" (the text must be
+    one).  Objects and arrays nest up to ``max_depth`` (<= PDA_DEPTH_MAX) levels; strings are well-formed UTF-8 without raw bytes below
+    0x20, the escapes are ``\\" \\\\ \\/ \\b \\f \\n \\r \\t \\uXXXX``; numbers are ``-?(0|[1-9][0-9]*)(\\.[0-9]+)?([eE][+-]?[0-9]+)?``; the
+    literals ``true false null``.  ``whitespace`` False: no whitespace outside strings (``json.dumps(..., separators=(",", ":"))``); True:
+    ``[ \\t\\n\\r]*`` wherever JSON allows it.
+
+    Two stack symbols, one per open container: array and object.  Every move is a single one: "[" and "{" push, "]" and "}" pop, a ","
+    is dispatched on the top symbol (array: a value follows, object: a key), and a number - the one value without a closing byte of
+    its own - is ended by the "," / "]" / "}" (or whitespace) behind it, which makes in the number's states the move it makes behind
+    any other value."""
+    if root not in ("value", "object", "array"):
+        raise ValueError(f"json_grammar: root 'value', 'object' or 'array' (got {root!r})")
+    if not isinstance(max_depth, int) or not 0 <= max_depth <= PDA_DEPTH_MAX:
+        raise ValueError(f"json_grammar: max_depth {max_depth!r} outside 0..{PDA_DEPTH_MAX} (PDA_DEPTH_MAX)")
+    names, moves = [], {}                                       # moves[(state, top, byte)] = (next state, op, symbol)
+    tops = (0, _SYM_ARRAY, _SYM_OBJECT)
+
+    def state(name):
+        names.append(name)
+        return name
+
+    def on(src, byte_mask, dst, op=PDA_NONE, sym=0, top=tops):
+        for t in top:
+            for v in range(256):
+                if (byte_mask >> v) & 1:
+                    assert (src, t, v) not in moves, (src, t, v)
+                    moves[(src, t, v)] = (dst, op, sym)
+
+    def ch(text):
+        return _mask(*text.encode())
+
+    ws = _WS if whitespace else 0
+    first = state("root") if root != "value" else None
+    VAL, ARR0, OBJ0, KEY, COLON, AFTER = (state(n) for n in ("value", "array-open", "object-open", "key", "colon", "after"))
+
+    def string(prefix, done):
+        """The states of one string behind its opening quote; the closing quote goes to ``done``."""
+        S, E, U1, U2, U3, U4, C1, C2, C3, E0, ED, F0, F4 = (state(prefix + n) for n in
+                                                             ("str", "esc", "u1", "u2", "u3", "u4", "c1", "c2", "c3", "e0", "ed", "f0", "f4"))
+        on(S, _mask((0x20, 0x7F)) & ~ch('"\\'), S)
+        on(S, ch('"'), done)
+        on(S, ch("\\"), E)
+        on(E, ch('"\\/bfnrt'), S)
+        on(E, ch("u"), U1)
+        for a, b in ((U1, U2), (U2, U3), (U3, U4), (U4, S)):
+            on(a, _HEX, b)
+        # well-formed UTF-8 (Unicode table 3-7), as _UTF8_MULTI has it
+        cont = _mask((0x80, 0xBF))
+        on(S, _mask((0xC2, 0xDF)), C1)
+        on(S, _mask(0xE0), E0)
+        on(S, _mask((0xE1, 0xEC), 0xEE, 0xEF), C2)
+        on(S, _mask(0xED), ED)
+        on(S, _mask(0xF0), F0)
+        on(S, _mask((0xF1, 0xF3)), C3)
+        on(S, _mask(0xF4), F4)
+        on(C1, cont, S)
+        on(C2, cont, C1)
+        on(C3, cont, C2)
+        on(E0, _mask((0xA0, 0xBF)), C1)
+        on(ED, _mask((0x80, 0x9F)), C1)
+        on(F0, _mask((0x90, 0xBF)), C2)
+        on(F4, _mask((0x80, 0x8F)), C2)
+        return S
+
+    KSTR, VSTR = string("key-", COLON), string("", AFTER)
+    NEG, ZERO, INT, FRAC0, FRAC, EXP0, EXPS, EXP = (state(n) for n in ("minus", "zero", "int", "point", "frac", "e", "e-sign", "exp"))
+    digit = _mask((0x30, 0x39))
+
+    def value_start(src):
+        on(src, ch('"'), VSTR)
+        on(src, ch("-"), NEG)
+        on(src, ch("0"), ZERO)
+        on(src, _mask((0x31, 0x39)), INT)
+        on(src, ch("["), ARR0, PDA_PUSH, _SYM_ARRAY)
+        on(src, ch("{"), OBJ0, PDA_PUSH, _SYM_OBJECT)
+        for word in ("true", "false", "null"):
+            on(src, ch(word[0]), word + "1")
+
+    def value_end(src):
+        """Behind a complete value: "," and the closer of the container on top; with an empty stack nothing but whitespace."""
+        on(src, ch(","), VAL, top=(_SYM_ARRAY,))
+        on(src, ch("]"), AFTER, PDA_POP, top=(_SYM_ARRAY,))
+        on(src, ch(","), KEY, top=(_SYM_OBJECT,))
+        on(src, ch("}"), AFTER, PDA_POP, top=(_SYM_OBJECT,))
+        on(src, ws, AFTER)
+
+    for word in ("true", "false", "null"):
+        for i in range(1, len(word)):
+            state(word + str(i))
+        for i in range(1, len(word)):
+            on(word + str(i), ch(word[i]), word + str(i + 1) if i + 1 < len(word) else AFTER)
+    if first is not None:
+        on(first, ws, first)
+        if root == "object":
+            on(first, ch("{"), OBJ0, PDA_PUSH, _SYM_OBJECT)
+        else:
+            on(first, ch("["), ARR0, PDA_PUSH, _SYM_ARRAY)
+    value_start(VAL)
+    on(VAL, ws, VAL)
+    value_start(ARR0)
+    on(ARR0, ws, ARR0)
+    on(ARR0, ch("]"), AFTER, PDA_POP, top=(_SYM_ARRAY,))
+    on(OBJ0, ws, OBJ0)
+    on(OBJ0, ch('"'), KSTR)
+    on(OBJ0, ch("}"), AFTER, PDA_POP, top=(_SYM_OBJECT,))
+    on(KEY, ws, KEY)
+    on(KEY, ch('"'), KSTR)
+    on(COLON, ws, COLON)
+    on(COLON, ch(":"), VAL)
+    value_end(AFTER)
+    on(NEG, ch("0"), ZERO)
+    on(NEG, _mask((0x31, 0x39)), INT)
+    on(INT, digit, INT)
+    for src in (ZERO, INT):
+        on(src, ch("."), FRAC0)
+    on(FRAC0, digit, FRAC)
+    on(FRAC, digit, FRAC)
+    for src in (ZERO, INT, FRAC):
+        on(src, ch("eE"), EXP0)
+    on(EXP0, ch("+-"), EXPS)
+    for src in (EXP0, EXPS, EXP):
+        on(src, digit, EXP)
+    for src in (ZERO, INT, FRAC, EXP):
+        value_end(src)
+    # Every reachable configuration at a depth <= max_depth can finish, without a push: inside a string, a number, a literal or an
+    # escape some byte completes the token (the closing quote, a digit, the literal's next letter, a hex digit, a continuation byte);
+    # where a value is expected "0" is one; where a key is expected '"":0' is a member; behind a value the closer of the container on
+    # top is a move (the top symbol always names the container the state is in, so the closer that pops it is the one defined) and
+    # leaves a complete value one level down; with an empty stack "after" and the complete-number states accept.  max_depth only
+    # refuses pushes, and no state needs one.  (With root "object" / "array" and max_depth 0 the root state cannot push: the language
+    # is empty, as asked for.)
+    index = {n: i for i, n in enumerate(names)}
+    assert len(index) == len(names) and all(dst in index for dst, _, _ in moves.values())
+    n = len(names)
+    full = np.full((n, 3, 256), PDA_DEAD, dtype=np.uint16)
+    for (src, t, v), (dst, op, sym) in moves.items():
+        full[index[src], t, v] = pda_entry(index[dst], op, sym)
+    cols, class_of, keep = {}, [], []
+    for v in range(256):                                        # byte classes: bytes no (state, top) distinguishes share a column
+        key = full[:, :, v].tobytes()
+        if key not in cols:
+            cols[key] = len(keep)
+            keep.append(v)
+        class_of.append(cols[key])
+    accept = [1 if s in (AFTER, ZERO, INT, FRAC, EXP) else 0 for s in names]
+    return BytePDA(class_of, full[:, :, keep], accept, 2, max_depth, name=f"json({root}{', whitespace' if whitespace else ''})")
+
+
+def as_grammar(grammar):
+    """A ``ByteDFA`` or a ``BytePDA`` as it is, a pattern string compiled (to a ``ByteDFA``)."""
+    if isinstance(grammar, (ByteDFA, BytePDA)):
+        return grammar
+    if isinstance(grammar, str):
+        return compile_regex(grammar)
+    raise ValueError(f"grammar: a ByteDFA, a BytePDA or a pattern string (got {type(grammar).__name__})")
 
 
 class TokenBytes:

@@ -60,7 +60,9 @@ extern "C" {
  * Still 3: qlinear_beam_advance and qlinear_beam_gather (and the constant QL_BEAMS_MAX) added - purely additive; qlinear_step_logprobs, which
  * supplies their candidates, is unchanged.
  * Still 3: qlinear_grammar_mask (and the constants QL_GRAMMAR_TABLE_MAX, QL_GRAMMAR_STATES_MAX, QL_GRAMMAR_CHUNK) added - purely additive;
- * qlinear_history_constraints and the selection entry points are unchanged, they read the masked logits. */
+ * qlinear_history_constraints and the selection entry points are unchanged, they read the masked logits.
+ * Still 3: qlinear_pda_mask (and the constants QL_PDA_DEPTH_MAX, QL_PDA_LOCAL_MAX, QL_PDA_SYMS_MAX) added - purely additive;
+ * qlinear_grammar_mask is unchanged, a call takes the one or the other launch. */
 #define QLINEAR_ABI_VERSION 3
 
 /* activation dtypes */
@@ -697,6 +699,59 @@ int qlinear_history_constraints(void* logits, int64_t B, int64_t N, int64_t ldl,
 int qlinear_grammar_mask(void* logits, int64_t B, int64_t N, int64_t ldl, const int32_t* tok_off, const uint8_t* tok_bytes, int64_t n_tok,
                          int64_t n_bytes, const uint8_t* class_of, const uint16_t* table, const uint8_t* accept, const int32_t* cfg,
                          int32_t* state, int32_t* ticket, const int64_t* tok, const int32_t* row_state, int dtype, void* stream);
+
+/* JSON-constrained generation: the mask of a byte-level PUSHDOWN automaton over the vocabulary - deterministic, real-time (one move per
+ * byte, no empty moves), one bounded stack - in the place of qlinear_grammar_mask: one launch between qlinear_history_constraints (or
+ * qlinear_logit_penalties, or lm_head) and the selection entry points; a step takes this launch or qlinear_grammar_mask, never both.
+ * Edits logits (B, N) IN PLACE (row stride ldl, unit column stride).  Everything a row's grammar decides is read from device memory and
+ * the row's configuration - state and stack - is kept there and advanced by this launch, so ONE captured graph serves every grammar.
+ *   tok_off, tok_bytes, n_tok, n_bytes, class_of (B, 256), accept (B, QL_GRAMMAR_STATES_MAX + 1), tok, row_state: qlinear_grammar_mask's.
+ *   table (B, QL_GRAMMAR_TABLE_MAX) uint16: row b's moves, table[(s * (n_syms + 1) + top) * n_classes + class], top = 0 for an empty
+ *     stack and otherwise the symbol on top, in 1..n_syms.  An entry: bits 0 - 11 the next state (>= n_states - 0xFFF by convention -
+ *     is DEAD), bits 12 - 13 the op (0 none, 1 pop, 2 push, 3 DEAD), bits 14 - 15 the pushed symbol; 0xFFFF by convention = no move.
+ *     The start configuration is state 0 with an empty stack.
+ *   cfg (B, 4) int32: n_states (<= 0: the row has no grammar), eos_id (outside [0, N), -1 by convention: none), n_syms, max_depth.
+ *   state (B) int32: the row's state s, -1 = dead.  depth (B) int32: the symbols on the row's stack.  stack (B, QL_PDA_DEPTH_MAX)
+ *     uint8: the symbols, bottom first; entries at and past depth mean nothing.  ticket (B) int32: 0 between launches.
+ * For row b, in this order:
+ *   0. row_state given and the row's finished bit (bit 0 of [b][1]) set, or n_states <= 0: the row is left entirely untouched - nothing
+ *      is read past that, nothing is written.
+ *   6. (first, because everything below uses the clamped values) clamps: n_states to QL_GRAMMAR_STATES_MAX; n_syms to [0,
+ *      QL_PDA_SYMS_MAX]; max_depth to [0, QL_PDA_DEPTH_MAX]; n_classes = 1 + the largest entry of class_of[b]; then n_states to
+ *      QL_GRAMMAR_TABLE_MAX / ((n_syms + 1) * n_classes) (integer division).  A state outside [0, n_states), a depth outside [0,
+ *      max_depth], or - at a depth > 0 - a top symbol stack[b][depth - 1] outside 1..n_syms makes the row DEAD.  Offsets must satisfy
+ *      0 <= tok_off[id] <= tok_off[id + 1] <= n_bytes or the id is masked (the fed id: the row dies).  A corrupt row masks too much; it
+ *      never indexes out of range.
+ *   1. advance: tok given: (s', stack') = the walk of bytes(tok[b]) from (s, stack).  An id outside [0, N) or [0, n_tok), or one with an
+ *      empty byte string, moves nothing; tok null: nothing moves.  A dead row stays dead.
+ *   2. one move on byte x from a live (s, stack): e = table[(s * (n_syms + 1) + top) * n_classes + class_of[x]].  Dead when the next state
+ *      is >= n_states or the op is 3; op 1 pops - dead at depth 0; op 2 pushes its symbol - dead when the symbol is 0 or > n_syms or when
+ *      depth == max_depth.  Whenever a pop uncovers a symbol of the row's stack outside 1..n_syms, the walk is dead (clamp 6).
+ *   3. the window rule: ONE token's walk may never hold more than QL_PDA_LOCAL_MAX symbols above the lowest depth it has reached during
+ *      that walk - a push that would is dead.  (A thread keeps its own pushes in one 64-bit register, 2 bits per symbol, and reads the
+ *      row's stack only for what it pops below them.  For JSON the rule excludes a token with 33 or more net-unclosed openers.)
+ *      The fed id's walk in rule 1 obeys it as well.
+ *   4. mask: for every id in [0, N) other than eos_id: logits[b][id] = -inf (in the logits dtype) when bytes(id) is empty or its walk
+ *      from (s', stack') is dead.  For eos_id: logits[b][eos_id] = -inf unless s' is live and accepting and depth' == 0; a dead s'
+ *      leaves eos_id alone, so such a row ends.  No logit is read; an allowed entry keeps its bits; nothing outside [row, row + N) is
+ *      touched.
+ *   5. store, exactly once per launch: state[b] = s' (-1 when dead); when s' is live also depth[b] = depth' and the symbols the advance
+ *      pushed, stack[b][low .. depth') with low = the lowest depth the advance reached (entries below low keep their bytes, entries at
+ *      and past depth' are not written); a dead row keeps its depth and stack bytes.
+ * Grid ceil(N / QL_GRAMMAR_CHUNK) x B workgroups of 256 threads; each copies the row's class map, its stack and the live part of its
+ * table (n_states * (n_syms + 1) * n_classes entries) into LDS, computes (s', stack') itself and walks its own QL_GRAMMAR_CHUNK tokens.
+ * No workgroup reads in this launch anything another workgroup of this launch wrote: every one reads the OLD state, depth and stack;
+ * behind its last logit store and an agent-scope release it draws a ticket (one agent-scope atomic add on ticket[b]); the one that
+ * draws the last ticket makes the stores of rule 5 - ordinary vector stores - and puts the ticket back to 0.  Nothing spins or waits
+ * on another workgroup.  ticket[b] must be 0 when a launch starts.
+ * Errors as qlinear_grammar_mask's (depth and stack are required buffers, depth aligned to 4); B == 0 is QL_OK without a launch. */
+#define QL_PDA_DEPTH_MAX 64
+#define QL_PDA_LOCAL_MAX 32
+#define QL_PDA_SYMS_MAX 3
+int qlinear_pda_mask(void* logits, int64_t B, int64_t N, int64_t ldl, const int32_t* tok_off, const uint8_t* tok_bytes, int64_t n_tok,
+                     int64_t n_bytes, const uint8_t* class_of, const uint16_t* table, const uint8_t* accept, const int32_t* cfg,
+                     int32_t* state, int32_t* depth, uint8_t* stack, int32_t* ticket, const int64_t* tok, const int32_t* row_state,
+                     int dtype, void* stream);
 
 /* Beam search inside the decode step.  P prompts x B beams (1 <= B <= QL_BEAMS_MAX) are R = P * B batch rows; rows g*B .. g*B+B-1 are
  * group g, every row of a group holds the same prompt.  A beam step is the model step's launches plus three: qlinear_step_logprobs on a
