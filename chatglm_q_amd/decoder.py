@@ -19,7 +19,7 @@ a tokenizer object with ``encode`` / ``decode`` may be supplied and is used if p
 from __future__ import annotations
 
 import time
-from typing import Iterable, Optional
+from typing import Iterable, NamedTuple, Optional
 
 import torch
 from torch import Tensor
@@ -48,6 +48,56 @@ def filtered_distribution(logits: Tensor, top_k: int = 100, top_p: float = 0.8, 
     before = torch.cumsum(probs, dim=-1) - probs
     probs = torch.where(before > top_p, torch.zeros_like(probs), probs)
     return probs / probs.sum(dim=-1, keepdim=True), indices
+
+
+# The logit stages of a decode step, in launch order, between lm_head and the selection ("The step plan"): the tag of the graph
+# key, the session attribute that holds the stage's state, its ``fused_ops`` function (looked up through the module at call time) and
+# whether the call also takes ``rows.live`` (the history constraints finish rows on their stop sequences).
+LOGIT_STAGES = (
+    ("pen", "pen", "logit_penalties", False),
+    ("con", "con", "history_constraints", True),
+    ("gr", "gr", "grammar_mask", False),
+    ("pda", "pda", "pda_mask", False),
+)
+
+
+class StepPlan(NamedTuple):
+    """Which launches make up one decode step behind lm_head, in order: the logit ``stages`` (tags of LOGIT_STAGES), the selection of
+    ``selector`` - "logits" (the host decides), "greedy", "sample", "rows" or "beam" - and, with ``lp``, the log-prob record's.  ``key``
+    names the captured graph: "greedy", "sample+pen", "rows+pen+con+gr+lp", ...  A "beam" step has neither stages nor record.  A
+    "logits" step launches neither and its key is bare: ``stages`` / ``lp`` then say what the caller applies to the logits it gets back."""
+    selector: str
+    stages: tuple
+    lp: bool
+    key: str
+
+    @property
+    def in_step(self) -> tuple:
+        """The stages the step itself launches."""
+        return () if self.selector == "logits" else self.stages
+
+
+_PLANS: dict = {}
+
+
+def step_plan(greedy: bool = True, sample: bool = False, rows: bool = False, pen: bool = False, lp: bool = False, con: bool = False,
+              beam: bool = False, gr: bool = False, pda: bool = False) -> StepPlan:
+    """The plan of the step ``DecodeSession.capture`` / ``decode_step`` are asked for with these flags (memoised: one lookup per step).
+    ``beam`` wins over the other selectors, ``rows`` over ``sample`` over ``greedy``."""
+    flags = (greedy, sample, rows, pen, lp, con, beam, gr, pda)
+    plan = _PLANS.get(flags)
+    if plan is None:
+        selector = "beam" if beam else "rows" if rows else "sample" if sample else "greedy" if greedy else "logits"
+        on = dict(pen=pen, con=con, gr=gr, pda=pda)
+        stages = tuple(tag for tag, _, _, _ in LOGIT_STAGES if on[tag])
+        if selector == "beam":                                  # the beam search's step: no sampling controls, no record
+            plan = StepPlan(selector, (), False, selector)
+        elif selector == "logits":                              # the host decides: it adjusts and records what it gets back
+            plan = StepPlan(selector, stages, bool(lp), selector)
+        else:                                                   # "greedy+pen", "sample+lp", "rows+pen+con+gr+lp", ...: graphs of their own
+            plan = StepPlan(selector, stages, bool(lp), "+".join((selector,) + stages + (("lp",) if lp else ())))
+        _PLANS[flags] = plan
+    return plan
 
 
 # hook of the developer experiments (chatglm_q_amd/dev/experiments.py); None in the product
@@ -355,11 +405,7 @@ class DecodeSession:
         B = self.batch
 
         def per_row(name, v):
-            if isinstance(v, (list, tuple)):
-                if len(v) != B:
-                    raise ValueError(f"arm_penalties: {name} has {len(v)} entries for {B} rows")
-                return list(v)
-            return [v] * B
+            return fused_ops.per_row(name, v, B, "arm_penalties")
 
         if len(prompts) != B:
             raise ValueError(f"arm_penalties: {len(prompts)} prompts for {B} rows")
@@ -377,11 +423,32 @@ class DecodeSession:
         self.pen.arm(prompts, settings, biases)
         return True
 
-    def penalize_first(self, logits: Tensor, rows: bool = False) -> Tensor:
-        """The armed sampling controls applied in place to a prefill's last-position logits (nothing generated yet: no count)."""
+    def _apply_stages(self, stages, logits: Tensor, tok: Optional[Tensor], rows: bool = False) -> Tensor:
+        """Launch the logit stages with these tags on `logits` (batch, vocab), in place and in LOGIT_STAGES' order: ``tok`` = the ids the
+        step was fed (None: the first token after a prefill - nothing is counted, appended or walked), ``rows``: the batched
+        generation's rows (finished ones are left alone).  Returns the adjusted logits."""
         from . import fused_ops
         lg = logits if logits.stride(-1) == 1 else logits.contiguous()
-        return fused_ops.logit_penalties(lg, self.pen, None, self.rows.row_state if rows else None)
+        row_state, live = (self.rows.row_state, self.rows.live) if rows else (None, None)
+        for tag, attr, fn, takes_live in LOGIT_STAGES:
+            if tag in stages:
+                getattr(fused_ops, fn)(lg, getattr(self, attr), tok, row_state, *((live,) if takes_live else ()))
+        return lg
+
+    def first_logits(self, plan: StepPlan, logits: Tensor) -> Tensor:
+        """The plan's logit stages applied in place to a prefill's last-position logits, in front of the first selection: nothing is
+        generated yet, so the penalties see the prompt ids and the bias only, the constraints the bans the prompt alone decides, and
+        every automaton stays at its start."""
+        return self._apply_stages(plan.stages, logits, None, plan.selector == "rows")
+
+    def host_logits(self, plan: StepPlan, logits: Tensor) -> Tensor:
+        """The host-sampled mode: the plan's logit stages applied in place to the logits ``decode_step`` returned - ``tok`` holds the id
+        that step was fed - in front of the host's own sampler."""
+        return self._apply_stages(plan.stages, logits, self.tok.view(-1))
+
+    def penalize_first(self, logits: Tensor, rows: bool = False) -> Tensor:
+        """The armed sampling controls applied in place to a prefill's last-position logits (nothing generated yet: no count)."""
+        return self._apply_stages(("pen",), logits, None, rows)
 
     def arm_constraints(self, prompts, no_repeat_ngram_size=0, bad_words_ids=None, stop_sequences=None, min_new_tokens=0,
                         eos_id=None, checked=None) -> bool:
@@ -412,15 +479,14 @@ class DecodeSession:
     def constrain_first(self, logits: Tensor, rows: bool = False) -> Tensor:
         """The armed history constraints applied in place to a prefill's last-position logits (nothing generated yet: nothing is
         appended) - behind ``penalize_first``, in front of the first selection."""
-        from . import fused_ops
-        lg = logits if logits.stride(-1) == 1 else logits.contiguous()
-        return fused_ops.history_constraints(lg, self.con, None, self.rows.row_state if rows else None, self.rows.live if rows else None)
+        return self._apply_stages(("con",), logits, None, rows)
 
     def arm_grammar(self, grammars, eos_id=None, token_bytes=None) -> bool:
         """Arm the grammars for a new generation (``fused_ops.GrammarState.arm``): ``grammars`` = one ``grammar.ByteDFA`` / pattern string /
         None for every row, or one per row (None: the row is unconstrained); ``eos_id``: the id a row may choose exactly when its
         output is a full match (one, or one per row; None: none).  ``token_bytes`` (``grammar.TokenBytes``): the vocabulary's byte
         table - needed by the first armed generation, kept afterwards; a different one replaces the buffers and drops the "+gr" graphs.
+        With a ``grammar.BytePDA`` among the rows the same goes for ``self.pda`` (``fused_ops.PdaState.arm``) and the "+pda" graphs.
         Every state starts at 0.  Returns whether any row has a grammar; with none nothing is armed - and nothing allocated - and the
         generation takes the steps without the launch."""
         from . import fused_ops
@@ -433,46 +499,37 @@ class DecodeSession:
             self.pda.active = False
         if all(d is None for d in dfas):
             return False
-        if any(isinstance(d, BytePDA) for d in dfas):           # one pushdown row: the whole call takes the "+pda" launch
-            return self._arm_pda(dfas, eos_id, token_bytes)
-        dfas, eos = fused_ops.GrammarState.check(B, dfas, eos_id, vocab=self.model.config.vocab_size)
-        if token_bytes is None and self.gr is None:
+        # one pushdown row: the whole call takes the "+pda" launch, every row's grammar goes into ``self.pda`` (a ``ByteDFA`` lifted by
+        # ``BytePDA.from_dfa``) and ``self.gr`` stays as it is and is not launched
+        tag, cls = ("pda", fused_ops.PdaState) if any(isinstance(d, BytePDA) for d in dfas) else ("gr", fused_ops.GrammarState)
+        vocab = self.model.config.vocab_size
+        automata, eos = cls.check(B, dfas, eos_id, vocab=vocab)
+        state = getattr(self, tag)
+        if token_bytes is None and state is None:
             raise ValueError("arm_grammar: a grammar needs the vocabulary's byte table (token_bytes=, grammar.token_byte_table builds one)")
-        if self.gr is None or (token_bytes is not None and token_bytes is not self._gr_source):
-            if self.gr is not None:                             # other buffers: the graphs that baked the old ones in go
-                for mode in [m for m in self._graphs if "+gr" in m]:
-                    self._graphs.pop(mode, None)
-                    self._graph_logits.pop(mode, None)
-                if self._captured_mode is not None and "+gr" in self._captured_mode:
-                    self.graph = self._captured_mode = None
-            vocab = self.model.config.vocab_size
+        if state is None or (token_bytes is not None and token_bytes is not getattr(self, f"_{tag}_source")):
+            if state is not None:                               # other buffers: the graphs that baked the old ones in go
+                self._drop_graphs(lambda key: "+" + tag in key)
             table = token_bytes.padded(vocab) if len(token_bytes) < vocab else token_bytes   # a padded vocabulary's extra ids are empty
-            self.gr = fused_ops.GrammarState(B, table, self.device)
-            self._gr_source = token_bytes
-        self.gr.arm(dfas, eos)
+            state = cls(B, table, self.device)
+            setattr(self, tag, state)
+            setattr(self, f"_{tag}_source", token_bytes)
+        state.arm(automata, eos)
         return True
 
-    def _arm_pda(self, grammars, eos_id, token_bytes) -> bool:
-        """``arm_grammar`` for a call with a ``grammar.BytePDA`` among its rows: every row's grammar goes into ``self.pda``
-        (``fused_ops.PdaState.arm``, a ``ByteDFA`` lifted by ``BytePDA.from_dfa``), ``self.gr`` stays as it is and is not launched."""
-        from . import fused_ops
-        B = self.batch
-        pdas, eos = fused_ops.PdaState.check(B, grammars, eos_id, vocab=self.model.config.vocab_size)
-        if token_bytes is None and self.pda is None:
-            raise ValueError("arm_grammar: a grammar needs the vocabulary's byte table (token_bytes=, grammar.token_byte_table builds one)")
-        if self.pda is None or (token_bytes is not None and token_bytes is not self._pda_source):
-            if self.pda is not None:                            # other buffers: the graphs that baked the old ones in go
-                for mode in [m for m in self._graphs if "+pda" in m]:
-                    self._graphs.pop(mode, None)
-                    self._graph_logits.pop(mode, None)
-                if self._captured_mode is not None and "+pda" in self._captured_mode:
-                    self.graph = self._captured_mode = None
-            vocab = self.model.config.vocab_size
-            table = token_bytes.padded(vocab) if len(token_bytes) < vocab else token_bytes
-            self.pda = fused_ops.PdaState(B, table, self.device)
-            self._pda_source = token_bytes
-        self.pda.arm(pdas, eos)
-        return True
+    def grammar_stage(self, armed: bool) -> dict:
+        """The step keywords of what the last ``arm_grammar`` (which returned ``armed``) armed: the pushdown launch ("+pda") in the
+        DFA launch's ("+gr") place when a row's grammar is a ``BytePDA``."""
+        pda = bool(armed) and self.pda_armed
+        return dict(gr=bool(armed) and not pda, pda=pda)
+
+    def _drop_graphs(self, predicate) -> None:
+        """Forget the captured steps whose key ``predicate`` accepts (something they baked in has changed)."""
+        for key in [k for k in self._graphs if predicate(k)]:
+            self._graphs.pop(key, None)
+            self._graph_logits.pop(key, None)
+        if self._captured_mode is not None and predicate(self._captured_mode):
+            self.graph = self._captured_mode = None
 
     @property
     def pda_armed(self) -> bool:
@@ -482,16 +539,12 @@ class DecodeSession:
     def pda_first(self, logits: Tensor, rows: bool = False) -> Tensor:
         """``grammar_first`` of the pushdown launch: the armed automata applied in place to a prefill's last-position logits (nothing
         generated yet: every configuration stays at its start)."""
-        from . import fused_ops
-        lg = logits if logits.stride(-1) == 1 else logits.contiguous()
-        return fused_ops.pda_mask(lg, self.pda, None, self.rows.row_state if rows else None)
+        return self._apply_stages(("pda",), logits, None, rows)
 
     def grammar_first(self, logits: Tensor, rows: bool = False) -> Tensor:
         """The armed grammars applied in place to a prefill's last-position logits (nothing generated yet: every state stays at its
         start) - behind ``constrain_first``, in front of the first selection."""
-        from . import fused_ops
-        lg = logits if logits.stride(-1) == 1 else logits.contiguous()
-        return fused_ops.grammar_mask(lg, self.gr, None, self.rows.row_state if rows else None)
+        return self._apply_stages(("gr",), logits, None, rows)
 
     def arm_logprobs(self, on: bool = True) -> bool:
         """Arm the log-prob record for a new generation (``fused_ops.StepLogprobs``: allocated on first use, one entry per cache
@@ -536,10 +589,7 @@ class DecodeSession:
             self._beam_table = fused_ops.BeamGatherTable(list(self.cache.k) + list(self.cache.v))
         self.beams.arm(self.batch // B, B, eos_id, length_penalty, early_stopping, first)
         if self._beams_B is not None and self._beams_B != B:
-            self._graphs.pop("beam", None)
-            self._graph_logits.pop("beam", None)
-            if self._captured_mode == "beam":
-                self.graph = self._captured_mode = None
+            self._drop_graphs(lambda key: key == "beam")
             self._beams_B = None
         return self.beams
 
@@ -561,11 +611,7 @@ class DecodeSession:
         budget per row, and the stop id (None: none).  The captured "rows" step bakes the stop id in: a different one drops it."""
         self.rows.arm(params, seeds, budgets, stop_id)
         if self._rows_stop is not None and self._rows_stop != self.rows.stop_id:
-            for mode in [m for m in self._graphs if m.startswith("rows")]:       # "rows", "rows+pen", "rows+con+lp", "rows+pen+lp", ...
-                self._graphs.pop(mode, None)
-                self._graph_logits.pop(mode, None)
-            if self._captured_mode is not None and self._captured_mode.startswith("rows"):
-                self.graph = self._captured_mode = None
+            self._drop_graphs(lambda key: key.startswith("rows"))   # "rows", "rows+pen", "rows+con+lp", "rows+pen+lp", ...
             self._rows_stop = None
 
     def sample_rows_first(self, logits: Tensor) -> None:
@@ -574,60 +620,40 @@ class DecodeSession:
         from . import fused_ops
         fused_ops.batch_sample_advance(logits, self.tok.view(-1), self.rows)
 
-    def _step_body(self, greedy: bool, sample: bool = False, rows: bool = False, pen: bool = False, lp: bool = False, con: bool = False,
-                   beam: bool = False, gr: bool = False, pda: bool = False):
+    def _step_body(self, plan: StepPlan):
         # invariant on entry: mask is 0 for positions <= write_index (the new position may attend to itself)
-        logits = self.model.step(self.tok, self.cache, self.write_index, self.pos, self.mask, last_only=True)
-        if beam:                                                # candidates, cross-beam selection + bookkeeping, cache reorder: three launches
-            from . import fused_ops
+        from . import fused_ops
+        logits = self.model.step(self.tok, self.cache, self.write_index, self.pos, self.mask, last_only=True)[:, -1]
+        tok = self.tok.view(-1)
+        if plan.selector == "beam":                             # candidates, cross-beam selection + bookkeeping, cache reorder: three launches
             st = self.beams
-            fused_ops.step_logprobs(logits[:, -1], self.tok.view(-1), st.cand)
-            fused_ops.beam_advance(st, self.tok.view(-1), self.write_index, self.pos.view(-1), self.mask)
+            fused_ops.step_logprobs(logits, tok, st.cand)
+            fused_ops.beam_advance(st, tok, self.write_index, self.pos.view(-1), self.mask)
             fused_ops.beam_gather(self._beam_table, st.parent, st.first, self.write_index, st.B)
             return
-        if pen and (greedy or sample or rows):                  # count the id this step was fed, adjust the logits in place: one launch
-            from . import fused_ops                             # in front of the selection (the host-sampled mode adjusts what it gets back)
-            fused_ops.logit_penalties(logits[:, -1], self.pen, self.tok.view(-1), self.rows.row_state if rows else None)
-        if con and (greedy or sample or rows):                  # append the id this step was fed, stop / ban on the history: one launch
-            from . import fused_ops                             # behind the penalties', in front of the selection
-            fused_ops.history_constraints(logits[:, -1], self.con, self.tok.view(-1), self.rows.row_state if rows else None,
-                                          self.rows.live if rows else None)
-        if gr and (greedy or sample or rows):                   # walk the id this step was fed, mask what the automaton does not survive:
-            from . import fused_ops                             # one launch behind the history constraints', in front of the selection
-            fused_ops.grammar_mask(logits[:, -1], self.gr, self.tok.view(-1), self.rows.row_state if rows else None)
-        if pda and (greedy or sample or rows):                  # ... or the pushdown automata's launch in its place: still one launch
-            from . import fused_ops
-            fused_ops.pda_mask(logits[:, -1], self.pda, self.tok.view(-1), self.rows.row_state if rows else None)
+        rows = plan.selector == "rows"
+        # one launch per stage on the id this step was fed, the logits adjusted in place, in front of the selection (the host-decides
+        # mode adjusts what it gets back)
+        logits = self._apply_stages(plan.in_step, logits, tok, rows)
         if rows:                                                # per-row selection, recording, stop + the bookkeeping: one launch;
-            from . import fused_ops                             # the tokens live in rows.out_tokens (self.logits is not touched)
-            fused_ops.batch_sample_advance(logits[:, -1], self.tok.view(-1), self.rows, self.write_index, self.pos.view(-1),
-                                           self.mask)
-            if lp:                                              # the record's launch, directly behind the selection (all three modes)
-                fused_ops.step_logprobs(logits[:, -1], self.tok.view(-1), self.lp, self.rows.row_state)
-            return
-        self.logits = logits[:, -1]
-        if sample:                                              # the reference's sampler + the bookkeeping: one launch
-            from . import fused_ops
-            lg = self.logits if self.logits.stride(-1) == 1 else self.logits.contiguous()
-            fused_ops.top_p_sample(lg, self.tok.view(-1), self.rng_state, dev_params=self.sample_params,
-                                   write_index=self.write_index, pos=self.pos.view(-1), mask=self.mask)
-            if lp:
-                fused_ops.step_logprobs(lg, self.tok.view(-1), self.lp)
-            return
-        if greedy and self.logits.is_cuda and self.logits.stride(-1) == 1:
-            from . import fused_ops
-            fused_ops.greedy_advance(self.logits, self.tok, self.write_index, self.pos, self.mask)   # one launch
-            if lp:
-                fused_ops.step_logprobs(self.logits, self.tok.view(-1), self.lp)
-            return
-        if greedy:
-            self.tok.copy_(self.logits.argmax(dim=-1, keepdim=True))
-            if lp:                                              # (CPU: the host form)
-                from . import fused_ops
-                fused_ops.step_logprobs(self.logits, self.tok.view(-1), self.lp)
-        self.write_index.add_(1)
-        self.pos.add_(1)
-        self.mask.index_fill_(2, torch.clamp(self.write_index, max=self.capacity - 1), 0.0)
+            # the tokens live in rows.out_tokens (self.logits is not touched)
+            fused_ops.batch_sample_advance(logits, tok, self.rows, self.write_index, self.pos.view(-1), self.mask)
+        else:
+            self.logits = logits
+            if plan.selector == "sample":                       # the reference's sampler + the bookkeeping: one launch
+                logits = logits if logits.stride(-1) == 1 else logits.contiguous()
+                fused_ops.top_p_sample(logits, tok, self.rng_state, dev_params=self.sample_params,
+                                       write_index=self.write_index, pos=self.pos.view(-1), mask=self.mask)
+            elif plan.selector == "greedy" and logits.is_cuda and logits.stride(-1) == 1:
+                fused_ops.greedy_advance(logits, self.tok, self.write_index, self.pos, self.mask)   # one launch
+            else:
+                if plan.selector == "greedy":
+                    self.tok.copy_(logits.argmax(dim=-1, keepdim=True))
+                self.write_index.add_(1)
+                self.pos.add_(1)
+                self.mask.index_fill_(2, torch.clamp(self.write_index, max=self.capacity - 1), 0.0)
+        if plan.lp and plan.selector != "logits":               # the record's launch, directly behind the selection (CPU: the host form)
+            fused_ops.step_logprobs(logits, tok, self.lp, self.rows.row_state if rows else None)
 
     def drop_canonical(self) -> int:
         """Low-footprint mode: free the canonical buffers of every int4 module that can serve without them, and the plain copies of a
@@ -675,17 +701,6 @@ class DecodeSession:
                             getattr(m, "act_quant", None)))
         return tuple(key)
 
-    @staticmethod
-    def _mode(greedy: bool, sample: bool, rows: bool = False, pen: bool = False, lp: bool = False, con: bool = False,
-              beam: bool = False, gr: bool = False, pda: bool = False) -> str:
-        if beam:                                                # the beam search's step: no sampling controls, no record
-            return "beam"
-        mode = "rows" if rows else ("sample" if sample else ("greedy" if greedy else "logits"))
-        if mode == "logits":                                    # the host decides: it adjusts and records what it gets back
-            return mode
-        # "greedy+pen", "sample+lp", "greedy+gr", "rows+pen+con+gr+lp", ...: graphs of their own
-        return mode + ("+pen" if pen else "") + ("+con" if con else "") + ("+gr" if gr else "") + ("+pda" if pda else "") + ("+lp" if lp else "")
-
     @property
     def _captured_greedy(self):                                 # kept for the developer tools that read it
         return self._captured_mode == "greedy"
@@ -693,36 +708,29 @@ class DecodeSession:
     @torch.no_grad()
     def capture(self, greedy: bool = True, sample: bool = False, rows: bool = False, pen: bool = False, lp: bool = False,
                 con: bool = False, beam: bool = False, gr: bool = False, pda: bool = False):
-        """Capture one decode step of the mode - "sample": the device sampler picks the next token, "greedy": the argmax does,
-        "rows": the batched generation's per-row kernel does (arm_rows), "logits": the host decides - or keep the captured one while nothing it bakes in has changed.  Graphs of several modes live
-        side by side (a decoder that alternates greedy and sampled generations captures each once).  ``pen``: the step with the sampling
-        controls' launch (arm_penalties) between lm_head and the selection - "greedy+pen" / "sample+pen" / "rows+pen", captured
-        next to the plain ones, which stay as they are.  ``lp``: the step with the log-prob record's launch (arm_logprobs) behind the
-        selection - "greedy+lp", "rows+pen+lp", ... - again graphs of their own.  ``con``: the step with the history constraints' launch
-        (arm_constraints) behind the penalties' and in front of the selection - "greedy+con", "rows+pen+con+lp", ... - likewise.
-        ``beam``: the beam search's step (arm_beams) - "beam", captured next to the others.  ``gr``: the step with the grammar's launch
-        (arm_grammar) behind the history constraints' and in front of the selection - "greedy+gr", "rows+pen+con+gr+lp", ... - graphs of
-        their own as well; tables and states are device memory, so one graph serves every pattern.  ``pda``: the step with the pushdown
-        automata's launch (arm_grammar with a ``grammar.BytePDA`` among the rows) in the grammar launch's place - "greedy+pda", ..."""
+        """Capture one decode step of the plan these flags ask for (``step_plan``; DESIGN.md, "The step plan", lists the selectors, the
+        stages, their order and the graph keys) - or keep the captured one while nothing it bakes in has changed.  Graphs of several
+        plans live side by side under their keys (a decoder that alternates greedy and sampled generations captures each once); tables
+        and states are device memory, so one graph serves every setting.  Every state a flag names must be armed first."""
+        self._capture(step_plan(greedy, sample, rows, pen, lp, con, beam, gr, pda))
+
+    # what arms each stage's state: named by the error of a capture that comes before it
+    _ARMED_BY = {"pen": "arm_penalties", "con": "arm_constraints", "gr": "arm_grammar", "pda": "arm_grammar with a BytePDA"}
+
+    def _capture(self, plan: StepPlan):
         if not self.use_graph:
             return
         from . import _lib
-        mode = self._mode(greedy, sample, rows, pen, lp, con, beam, gr, pda)
-        pen, lp, con, gr, pda = "+pen" in mode, mode.endswith("+lp"), "+con" in mode, "+gr" in mode, "+pda" in mode
-        if beam:
-            greedy = sample = rows = False
-            if self.beams is None or self.beams.B < 1:
-                raise RuntimeError("capture(beam=True) before arm_beams")
-        if pen and self.pen is None:
-            raise RuntimeError("capture(pen=True) before arm_penalties")
-        if con and self.con is None:
-            raise RuntimeError("capture(con=True) before arm_constraints")
+        mode, rows, beam = plan.key, plan.selector == "rows", plan.selector == "beam"
+        lp = plan.lp and plan.selector != "logits"
+        if beam and (self.beams is None or self.beams.B < 1):
+            raise RuntimeError("capture(beam=True) before arm_beams")
+        stage_states = [(tag, getattr(self, attr)) for tag, attr, _, _ in LOGIT_STAGES if tag in plan.in_step]
+        for tag, st in stage_states:
+            if st is None:
+                raise RuntimeError(f"capture({tag}=True) before {self._ARMED_BY[tag]}")
         if lp and self.lp is None:
             raise RuntimeError("capture(lp=True) before arm_logprobs")
-        if gr and self.gr is None:
-            raise RuntimeError("capture(gr=True) before arm_grammar")
-        if pda and self.pda is None:
-            raise RuntimeError("capture(pda=True) before arm_grammar with a BytePDA")
         if self._graphs:
             # cheap test first (a process-wide counter every derived-layout build / drop bumps), the full fingerprint when it moved
             valid = self._graph_epoch == _lib.layout_epoch() and self._graph_versions == self._canonical_versions()
@@ -742,9 +750,10 @@ class DecodeSession:
         # entry counts: they must record nothing - what they wrote past the count is overwritten by the steps that follow; and the
         # history constraints' lengths: they must append nothing that survives - a row they stop comes back with row_state / live; and
         # the grammars' states: the warm-up runs must not walk them)
-        state = ((self.tok, self.write_index, self.pos, self.mask, self.rng_state) + self.rows.tensors()
-                 + (self.pen.tensors() if pen else ()) + ((self.lp.count,) if lp else ()) + (self.con.tensors() if con else ())
-                 + (self.gr.tensors() if gr else ()) + (self.pda.tensors() if pda else ()) + (self.beams.tensors() + (self.beams.first,) if beam else ()))
+        state = (self.tok, self.write_index, self.pos, self.mask, self.rng_state) + self.rows.tensors()
+        for _, st in stage_states:
+            state += st.tensors()
+        state += ((self.lp.count,) if lp else ()) + (self.beams.tensors() + (self.beams.first,) if beam else ())
         saved = tuple(t.clone() for t in state)
         if beam:
             # the warm-up's gathers touch only cache positions its own steps write, [write_index now, write_index then): every one of
@@ -753,20 +762,20 @@ class DecodeSession:
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
-            self._step_body(greedy, sample, rows, pen, lp, con, beam, gr, pda)          # warm-up: allocations, lazy repacks
+            self._step_body(plan)                               # warm-up: allocations, lazy repacks
             # the warm-up built what the step reads (e.g. the gate-interleaved copy of w_in): what it made redundant goes now,
             # and the step runs once more so that every pre-bound launch exists before the capture
             if self.decode_only and self.release_prefill_layouts():
-                self._step_body(greedy, sample, rows, pen, lp, con, beam, gr, pda)
+                self._step_body(plan)
             if self.low_footprint and self.drop_canonical():
-                self._step_body(greedy, sample, rows, pen, lp, con, beam, gr, pda)      # the pre-bound launches re-validate against the stand-in buffers
+                self._step_body(plan)                           # the pre-bound launches re-validate against the stand-in buffers
         torch.cuda.current_stream(self.device).wait_stream(side)
         if self._graphs and self._graph_epoch != _lib.layout_epoch():
             self._graphs.clear()                                # this mode's warm-up rebuilt / dropped a layout the older graphs baked in
             self._graph_logits.clear()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            self._step_body(greedy, sample, rows, pen, lp, con, beam, gr, pda)
+            self._step_body(plan)
         # capture ran the body twice on live state: restore (the cache rows it touched get rewritten)
         for dst, src in zip(state, saved):
             dst.copy_(src)
@@ -806,36 +815,26 @@ class DecodeSession:
     def decode_step(self, token: Optional[Tensor] = None, greedy: bool = True, sample: bool = False, rows: bool = False,
                     pen: bool = False, lp: bool = False, con: bool = False, beam: bool = False, gr: bool = False,
                     pda: bool = False) -> Tensor:
-        """Advance by one token.  `token` (batch, 1) overrides the device-resident next id (needed when the
-        host samples).  ``sample``: the device sampler (set_sampling) draws the next id into ``tok``.  Returns this step's
-        last-position logits (batch, vocab).  ``rows``: the batched generation's step (arm_rows): every row selects, records and
-        stops on its own; returns None (the tokens are in ``rows.out_tokens``).  ``pen``: the armed sampling controls (arm_penalties)
-        count the id fed into the step and adjust the logits in front of the selection; the host-decides mode (neither greedy, sample
-        nor rows) returns the logits as the model gave them - its caller adjusts them (``fused_ops.logit_penalties``).  ``lp``: the
-        armed log-prob record (arm_logprobs) gets this step's entry behind the selection; the host-decides mode records nothing -
-        its caller does, with the id it chose (``fused_ops.step_logprobs``).  ``con``: the armed history constraints
-        (arm_constraints) append the id fed into the step, stop rows (``rows`` only) and ban entries behind the penalties and in
-        front of the selection; the host-decides mode leaves that to its caller too (``fused_ops.history_constraints``).  ``beam``:
-        the beam search's step (arm_beams): every row's candidates, the cross-beam selection and the cache reorder by parent beam;
-        returns None (the beams are in ``beams``).  ``gr``: the armed grammars (arm_grammar) walk the id fed into the step and mask
-        what their automata do not survive, behind the history constraints and in front of the selection; the host-decides mode leaves
-        that to its caller as well (``fused_ops.grammar_mask``).  ``pda``: the pushdown automata's launch in that place (``fused_ops.pda_mask``)."""
+        """Advance by one token: one step of the plan these flags ask for (``step_plan``; DESIGN.md, "The step plan").  `token`
+        (batch, 1) overrides the device-resident next id (needed when the host samples).  Returns this step's last-position logits
+        (batch, vocab) - in the host-decides mode (neither greedy, sample nor rows) as the model gave them: the caller applies the
+        stages and the record itself (``host_logits``, ``fused_ops.step_logprobs``) - or None for the "rows" and "beam" steps, whose
+        tokens are in ``rows.out_tokens`` / ``beams``."""
         if self.length + 1 > self.capacity:
             raise ValueError("cache capacity exhausted")
         if token is not None:
             self.tok.copy_(token.to(self.device))
-        mode = self._mode(greedy, sample, rows, pen, lp, con, beam, gr, pda)
-        pen, lp, con, gr, pda = "+pen" in mode, mode.endswith("+lp"), "+con" in mode, "+gr" in mode, "+pda" in mode
-        if mode in self._graphs:
+        plan = step_plan(greedy, sample, rows, pen, lp, con, beam, gr, pda)
+        if plan.key in self._graphs:
             from . import _lib
-            if self._graph_epoch != _lib.layout_epoch() or self._captured_mode != mode:   # a derived layout was rebuilt / dropped since
-                self.capture(greedy, sample, rows, pen, lp, con, beam, gr, pda)   # the capture: capture() compares the fingerprint and keeps the graphs
+            if self._graph_epoch != _lib.layout_epoch() or self._captured_mode != plan.key:   # a derived layout was rebuilt / dropped since
+                self._capture(plan)                             # the capture: _capture() compares the fingerprint and keeps the graphs
             self.graph.replay()                                 # when only modules of OTHER models / sessions moved (ADVICE r3)
         else:
-            self._step_body(greedy, sample, rows, pen, lp, con, beam, gr, pda)
+            self._step_body(plan)
         self.length += 1
         self.cache.length = self.length
-        return None if rows or beam else self.logits
+        return None if plan.selector in ("rows", "beam") else self.logits
 
 
 class SentencePieceIds:
@@ -1171,8 +1170,6 @@ class ChatGLMDecoder:
             pen = sess.arm_penalties([prefix], repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
             con = sess.arm_constraints([prefix], checked=con_settings)
             gr = dfa is not None and sess.arm_grammar([dfa], eos, tokens)
-            pda = gr and sess.pda_armed                            # a BytePDA: the "+pda" launch in the "+gr" launch's place
-            gr = gr and not pda
             dev_sample = (not greedy) and sess.device_sampler_serves(top_k) and device_sampler is not False
             if device_sampler and not greedy and not dev_sample:
                 raise ValueError(f"device_sampler=True needs a GPU and top_k <= 1024 (got {sess.device}, top_k {top_k})")
@@ -1180,14 +1177,14 @@ class ChatGLMDecoder:
                 if seed is None:
                     seed = int(torch.randint(0, 2 ** 62, (1,)).item())
                 sess.set_sampling(top_k, top_p, temperature, seed)
+            # the keywords of every capture / decode_step of this generation
+            step = dict(greedy=greedy, sample=dev_sample, pen=pen, lp=sess.arm_logprobs(n_lp is not None), con=con, **sess.grammar_stage(gr))
+            inner = self._generate(sess, prefix, budget, top_k, top_p, temperature, ignore_eos, prefill_chunk, sync_every_token, step,
+                                   stops, dfa)
             if n_lp is None:
-                yield from self._generate(sess, prefix, budget, top_k, top_p, temperature, greedy, ignore_eos, prefill_chunk,
-                                          sync_every_token, dev_sample, pen, con=con, stops=stops, gr=gr, dfa=dfa, pda=pda)
+                yield from inner
             else:
-                sess.arm_logprobs(True)
                 returned = 0
-                inner = self._generate(sess, prefix, budget, top_k, top_p, temperature, greedy, ignore_eos, prefill_chunk,
-                                       sync_every_token, dev_sample, pen, lp=True, con=con, stops=stops, gr=gr, dfa=dfa, pda=pda)
                 try:
                     for token in inner:
                         returned += 1
@@ -1201,24 +1198,18 @@ class ChatGLMDecoder:
             if POST_GENERATE_CHECK is not None:                 # set by chatglm_q_amd.dev.experiments: error words of one-launch MLPs
                 POST_GENERATE_CHECK(sess)
 
-    def _generate(self, sess: DecodeSession, prefix, budget: int, top_k: int, top_p: float, temperature: float, greedy: bool,
-                  ignore_eos: bool, prefill_chunk: Optional[int], sync_every_token: bool, dev_sample: bool = False, pen: bool = False,
-                  lp: bool = False, con: bool = False, stops=(), gr: bool = False, dfa=None, pda: bool = False):
+    def _generate(self, sess: DecodeSession, prefix, budget: int, top_k: int, top_p: float, temperature: float, ignore_eos: bool,
+                  prefill_chunk: Optional[int], sync_every_token: bool, step: dict, stops=(), dfa=None):
+        # ``step``: the keywords of this generation's capture / decode_step calls; its plan says what runs around them
+        plan = step_plan(**step)
+        greedy, dev_sample, lp = step["greedy"], step["sample"], plan.lp
         # `auto`: the device picks the next token inside the step (argmax or the one-launch sampler) and feeds it back itself
-        auto = greedy or dev_sample
+        auto = plan.selector != "logits"
         times = []
         sync = (lambda: torch.cuda.synchronize(sess.device)) if sess.device.type == "cuda" else (lambda: None)
 
         t0 = time.perf_counter()
-        logits = sess.prefill(torch.tensor([prefix], dtype=torch.long), prefill_chunk)
-        if pen:                                                    # nothing generated yet: prompt ids and the bias only
-            logits = sess.penalize_first(logits)
-        if con:                                                    # ... and the bans the prompt alone decides
-            logits = sess.constrain_first(logits)
-        if gr:                                                     # ... and what the pattern's start state does not survive
-            logits = sess.grammar_first(logits)
-        if pda:
-            logits = sess.pda_first(logits)
+        logits = sess.first_logits(plan, sess.prefill(torch.tensor([prefix], dtype=torch.long), prefill_chunk))
         if dev_sample:
             nxt = sess.sample_first(logits)
         else:
@@ -1238,7 +1229,7 @@ class ChatGLMDecoder:
         device_loop = auto and not sync_every_token and (ignore_eos or self.eos_token_id is None) and not stops
         if len(generated) < budget and (ignore_eos or token != self.eos_token_id) and not stopped():
             sess.tok.fill_(token)
-            sess.capture(greedy=greedy, sample=dev_sample, pen=pen, lp=lp, con=con, gr=gr, pda=pda)
+            sess.capture(**step)
         pending = []
         # Greedy or device-sampled decoding on a captured step: the graph feeds its own choice back, so step k + 1 does not wait for the HOST to have seen
         # token k.  It is launched before token k is read (one step of speculation: wasted - and harmless, the next prefill re-arms the
@@ -1251,7 +1242,7 @@ class ChatGLMDecoder:
             events = [torch.cuda.Event(), torch.cuda.Event()]
 
             def launch(k):
-                sess.decode_step(None, greedy=greedy, sample=dev_sample, pen=pen, lp=lp, con=con, gr=gr, pda=pda)
+                sess.decode_step(None, **step)
                 ring[k & 1].copy_(sess.tok.view(-1), non_blocking=True)
                 events[k & 1].record()
 
@@ -1276,30 +1267,20 @@ class ChatGLMDecoder:
             t0 = time.perf_counter()
             if device_loop:
                 # the graph feeds its own choice back as the next input: the host only replays
-                sess.decode_step(greedy=greedy, sample=dev_sample, pen=pen, lp=lp, con=con, gr=gr, pda=pda)
+                sess.decode_step(**step)
                 pending.append(sess.tok.clone())
                 generated.append(-1)
                 times.append(time.perf_counter() - t0)
                 continue
-            logits = sess.decode_step(None if auto else torch.tensor([[generated[-1]]]), greedy=greedy, sample=dev_sample, pen=pen,
-                                      lp=lp, con=con, gr=gr, pda=pda)
-            if pen and not auto:                                   # the host samples: it adjusts the logits it got back (tok = the id just fed)
-                from . import fused_ops
-                logits = fused_ops.logit_penalties(logits if logits.stride(-1) == 1 else logits.contiguous(), sess.pen, sess.tok.view(-1))
-            if con and not auto:                                   # ... and constrains them, behind the penalties
-                from . import fused_ops
-                logits = fused_ops.history_constraints(logits if logits.stride(-1) == 1 else logits.contiguous(), sess.con,
-                                                       sess.tok.view(-1))
-            if gr and not auto:                                    # ... and masks them, behind the history constraints
-                from . import fused_ops
-                logits = fused_ops.grammar_mask(logits if logits.stride(-1) == 1 else logits.contiguous(), sess.gr, sess.tok.view(-1))
-            if pda and not auto:
-                from . import fused_ops
-                logits = fused_ops.pda_mask(logits if logits.stride(-1) == 1 else logits.contiguous(), sess.pda, sess.tok.view(-1))
-            nxt = sess.tok[:, 0] if auto else top_p_sampling(logits, top_k, top_p, temperature)
-            if lp and not auto:                                    # ... and records its own choice on the logits it sampled from
-                from . import fused_ops
-                fused_ops.step_logprobs(logits, nxt.view(-1).contiguous(), sess.lp)
+            logits = sess.decode_step(None if auto else torch.tensor([[generated[-1]]]), **step)
+            if auto:
+                nxt = sess.tok[:, 0]
+            else:                                                  # the host samples: it adjusts, constrains and masks the logits it got back,
+                logits = sess.host_logits(plan, logits)            # draws from them and records its own choice on them
+                nxt = top_p_sampling(logits, top_k, top_p, temperature)
+                if lp:
+                    from . import fused_ops
+                    fused_ops.step_logprobs(logits, nxt.view(-1).contiguous(), sess.lp)
             token = int(nxt.item())
             times.append(time.perf_counter() - t0)
             generated.append(token)
@@ -1315,12 +1296,13 @@ class ChatGLMDecoder:
 
         n = len(times)
         rest = sum(times[1:])
+        grammar = "gr" in plan.stages or "pda" in plan.stages
         self.last_stats = {
             "prefix": len(prefix), "generated": n, "init_s": times[0], "sum_s": sum(times),
             "gen_tok_per_s": (n - 1) / rest if n > 1 and rest > 0 else float("nan"),
-            "avg_tok_per_s": n / sum(times), "penalties": bool(pen), "logprobs": bool(lp),
-            "constraints": bool(con or stops), "stop_sequence": matched_stop_sequence(generated, stops),
-            "grammar": bool(gr or pda), "grammar_state": self._grammar_result(dfa, generated, self.eos_token_id) if gr or pda else None,
+            "avg_tok_per_s": n / sum(times), "penalties": "pen" in plan.stages, "logprobs": lp,
+            "constraints": "con" in plan.stages or bool(stops), "stop_sequence": matched_stop_sequence(generated, stops),
+            "grammar": grammar, "grammar_state": self._grammar_result(dfa, generated, self.eos_token_id) if grammar else None,
         }
         if self.time_log:
             s = self.last_stats
@@ -1348,6 +1330,37 @@ class ChatGLMDecoder:
     # a larger group has nothing to win; an EOS run wasted 6 steps.
     BATCH_POLL_EVERY = 4
     SEED_STRIDE = 0x9E3779B97F4A7C15                            # seed=int: row b's seed is (seed + b * SEED_STRIDE) mod 2^63
+
+    def _replay_polled(self, sess: DecodeSession, step: dict, max_steps: int, poll: int, live: Tensor, extra: Optional[Tensor] = None) -> int:
+        """Capture the step ``step`` (the keywords of ``capture`` / ``decode_step``) and run it up to ``max_steps`` times, in groups of
+        ``poll`` between two looks at the count in ``live`` (one int32: rows / prompts still running; ``extra``: a tensor copied to
+        the host beside it); returns the steps run."""
+        sess.capture(**step)
+        cuda = sess.device.type == "cuda"
+        if cuda:
+            ring = torch.zeros((2, 1 + (extra.numel() if extra is not None else 0)), dtype=torch.int32).pin_memory()
+            events = [torch.cuda.Event(), torch.cuda.Event()]
+        steps = g = 0
+        while steps < max_steps:
+            n = min(poll, max_steps - steps)
+            for _ in range(n):
+                sess.decode_step(**step)
+            steps += n
+            if not cuda:
+                if int(live[0]) == 0:
+                    break
+                continue
+            ring[g & 1, :1].copy_(live, non_blocking=True)
+            if extra is not None:
+                ring[g & 1, 1:].copy_(extra.view(-1), non_blocking=True)
+            events[g & 1].record()
+            # the previous group's count: its event is behind the group the device is running now
+            if g > 0:
+                events[(g - 1) & 1].synchronize()
+                if int(ring[(g - 1) & 1, 0]) == 0:
+                    break
+            g += 1
+        return steps
 
     @torch.no_grad()
     def generate_batch_ids(self, prompts, max_generated_tokens=400, top_k=100, top_p=0.8, temperature=1.0, greedy=False,
@@ -1400,13 +1413,10 @@ class ChatGLMDecoder:
         if not prompts or any(len(p) == 0 for p in prompts):
             raise ValueError("generate_batch_ids: at least one prompt, none of them empty")
         B = len(prompts)
+        from . import fused_ops
 
         def per_row(name, v, conv):
-            if isinstance(v, (list, tuple)):
-                if len(v) != B:
-                    raise ValueError(f"generate_batch_ids: {name} has {len(v)} entries for {B} prompts")
-                return [conv(x) for x in v]
-            return [conv(v)] * B
+            return [conv(x) for x in fused_ops.per_row(name, v, B, "generate_batch_ids", "prompts")]
 
         wanted = per_row("max_generated_tokens", max_generated_tokens, int)
         ks, ps = per_row("top_k", top_k, int), per_row("top_p", top_p, float)
@@ -1416,7 +1426,6 @@ class ChatGLMDecoder:
         if any(k < 1 for k in ks):
             raise ValueError("generate_batch_ids: top_k >= 1")
         ks = [1 if g else k for g, k in zip(gr, ks)]
-        from . import fused_ops
         on_gpu = self.model.final_ln.weight.device.type == "cuda"
         if on_gpu and any(k > fused_ops.SAMPLER_MAX_TOP_K for k in ks) and self.model.config.vocab_size > fused_ops.SAMPLER_MAX_TOP_K:
             raise ValueError(f"generate_batch_ids: top_k <= {fused_ops.SAMPLER_MAX_TOP_K} on a GPU (got {max(ks)})")
@@ -1474,20 +1483,10 @@ class ChatGLMDecoder:
             pen = sess.arm_penalties(prompts, *pen_args)
             con = sess.arm_constraints(prompts, checked=con_settings)
             gr = tokens is not None and sess.arm_grammar(dfas, stop, tokens)
-            pda = gr and sess.pda_armed
-            gr = gr and not pda
             lp = sess.arm_logprobs(n_lp is not None)
-            cuda = sess.device.type == "cuda"
+            step = dict(greedy=False, rows=True, pen=pen, lp=lp, con=con, **sess.grammar_stage(gr))
             t0 = time.perf_counter()
-            logits = sess.prefill(ids, prefill_chunk, attention_mask=attn)
-            if pen:
-                logits = sess.penalize_first(logits, rows=True)
-            if con:
-                logits = sess.constrain_first(logits, rows=True)
-            if gr:
-                logits = sess.grammar_first(logits, rows=True)
-            if pda:
-                logits = sess.pda_first(logits, rows=True)
+            logits = sess.first_logits(step_plan(**step), sess.prefill(ids, prefill_chunk, attention_mask=attn))
             sess.sample_rows_first(logits)
             if lp:
                 sess.logprobs_first(logits, rows=True)
@@ -1495,29 +1494,7 @@ class ChatGLMDecoder:
             t_first = time.perf_counter() - t0
             steps, max_steps = 0, max(budgets) - 1
             if live > 0 and max_steps > 0:
-                sess.capture(greedy=False, rows=True, pen=pen, lp=lp, con=con, gr=gr, pda=pda)
-                if cuda:
-                    ring = torch.zeros((2, 1 + 2 * B), dtype=torch.int32).pin_memory()
-                    events = [torch.cuda.Event(), torch.cuda.Event()]
-                g = 0
-                while steps < max_steps:
-                    n = min(poll, max_steps - steps)
-                    for _ in range(n):
-                        sess.decode_step(greedy=False, rows=True, pen=pen, lp=lp, con=con, gr=gr, pda=pda)
-                    steps += n
-                    if not cuda:
-                        if int(sess.rows.live[0]) == 0:
-                            break
-                        continue
-                    ring[g & 1, :1].copy_(sess.rows.live, non_blocking=True)
-                    ring[g & 1, 1:].copy_(sess.rows.row_state.view(-1), non_blocking=True)
-                    events[g & 1].record()
-                    # the previous group's count: its event is behind the group the device is running now
-                    if g > 0:
-                        events[(g - 1) & 1].synchronize()
-                        if int(ring[(g - 1) & 1, 0]) == 0:
-                            break
-                    g += 1
+                steps = self._replay_polled(sess, step, max_steps, poll, sess.rows.live, sess.rows.row_state)
             out = sess.rows.out_tokens.cpu()                    # one copy of the tokens at the end
             state = sess.rows.row_state.cpu()
             total = time.perf_counter() - t0
@@ -1537,7 +1514,7 @@ class ChatGLMDecoder:
             "gen_tok_per_s": (gen - sum(1 for c in counts if c)) / rest if steps and rest > 0 else float("nan"),
             "avg_tok_per_s": gen / total if total > 0 else float("nan"), "penalties": bool(pen), "logprobs": bool(lp),
             "constraints": bool(con), "stop_sequence": [matched_stop_sequence(res[b], row_stops[b]) for b in range(B)],
-            "grammar": bool(gr or pda), "grammar_state": [self._grammar_result(dfas[b], res[b], stop) for b in range(B)],
+            "grammar": bool(gr), "grammar_state": [self._grammar_result(dfas[b], res[b], stop) for b in range(B)],
         }
         if self.time_log:
             s = self.last_stats
@@ -1607,7 +1584,6 @@ class ChatGLMDecoder:
         sess.busy = True
         try:
             st = sess.arm_beams(B, eos, length_penalty, early_stopping, first=S)
-            cuda = sess.device.type == "cuda"
             t0 = time.perf_counter()
             logits = sess.prefill(ids, prefill_chunk, attention_mask=attn)
             sess.beam_first(logits)
@@ -1615,28 +1591,7 @@ class ChatGLMDecoder:
             t_first = time.perf_counter() - t0
             steps, max_steps = 0, budget - 1
             if live > 0 and max_steps > 0:
-                sess.capture(greedy=False, beam=True)
-                if cuda:
-                    ring = torch.zeros((2, 1), dtype=torch.int32).pin_memory()
-                    events = [torch.cuda.Event(), torch.cuda.Event()]
-                g = 0
-                while steps < max_steps:
-                    n = min(poll, max_steps - steps)
-                    for _ in range(n):
-                        sess.decode_step(greedy=False, beam=True)
-                    steps += n
-                    if not cuda:
-                        if int(st.live[0]) == 0:
-                            break
-                        continue
-                    ring[g & 1].copy_(st.live, non_blocking=True)
-                    events[g & 1].record()
-                    # the previous group's count: its event is behind the group the device is running now
-                    if g > 0:
-                        events[(g - 1) & 1].synchronize()
-                        if int(ring[(g - 1) & 1, 0]) == 0:
-                            break
-                    g += 1
+                steps = self._replay_polled(sess, dict(greedy=False, beam=True), max_steps, poll, st.live)
             host = st.fetch()                                   # one copy of every buffer at the end
             norm = st.norm.cpu()
             total = time.perf_counter() - t0

@@ -555,6 +555,27 @@ def _finite(v) -> bool:
     return v == v and v not in (float("inf"), float("-inf"))
 
 
+def _check_step_logits(name: str, logits: Tensor, batch: int, tok, row_state, state_tensor: Tensor, kind: str | None = None):
+    """The argument checks the step's logit stages share (``name``: the caller, the prefix of every message): `logits` (B, N) with unit
+    column stride and rows that do not overlap, ``tok`` / ``row_state`` of B rows, everything on the logits' device.  ``kind`` (the state's
+    class name): B must be ``batch``; None: the caller compares the shape itself.  Returns (B, N)."""
+    if logits.dim() != 2 or logits.shape[1] < 1 or logits.stride(1) != 1:
+        raise ValueError(f"{name}: logits must be (B, N) with N >= 1 and unit column stride, got {tuple(logits.shape)}")
+    B, N = logits.shape
+    if kind is not None and B != batch:
+        raise ValueError(f"{name}: {B} logits rows for a {kind} of {batch}")
+    if B > 1 and logits.stride(0) < N:
+        raise ValueError(f"{name}: overlapping logits rows")
+    if tok is not None and (tok.dtype != torch.int64 or tok.numel() != B or not tok.is_contiguous()):
+        raise ValueError(f"{name}: tok must be a contiguous int64 tensor of B elements")
+    if row_state is not None and (row_state.dtype != torch.int32 or tuple(row_state.shape) != (B, 2) or not row_state.is_contiguous()):
+        raise ValueError(f"{name}: row_state must be a contiguous int32 (B, 2) tensor (BatchRows.row_state)")
+    for t in (state_tensor, tok, row_state):
+        if t is not None and t.device != logits.device:
+            raise ValueError(f"{name}: logits on {logits.device}, state on {t.device}")
+    return B, N
+
+
 class PenaltyState:
     """Static buffers of ``logit_penalties`` for a batch of rows (a captured step reads and updates them in place): ``counts``
     (batch, ld) int32 - bit 31: the entry is one of the row's prompt ids, bits 0..30: how often the row has generated it;
@@ -694,20 +715,9 @@ def logit_penalties(logits: Tensor, state: PenaltyState, tok: Tensor | None = No
     int64: the ids fed into this step - counted before the rules are applied; None (the first token after a prefill): nothing is
     counted.  ``row_state``: a ``BatchRows.row_state``; rows whose FINISHED bit is set are left untouched.  Returns `logits`.  CPU
     tensors take the host form (torch ops, the same rules bit for bit)."""
-    if logits.dim() != 2 or logits.shape[1] < 1 or logits.stride(1) != 1:
-        raise ValueError(f"logit_penalties: logits must be (B, N) with N >= 1 and unit column stride, got {tuple(logits.shape)}")
-    B, N = logits.shape
+    B, N = _check_step_logits("logit_penalties", logits, state.batch, tok, row_state, state.counts)
     if B != state.batch or N != state.vocab:
         raise ValueError(f"logit_penalties: logits {tuple(logits.shape)} for a PenaltyState of ({state.batch}, {state.vocab})")
-    if B > 1 and logits.stride(0) < N:
-        raise ValueError("logit_penalties: overlapping logits rows")
-    if tok is not None and (tok.dtype != torch.int64 or tok.numel() != B or not tok.is_contiguous()):
-        raise ValueError("logit_penalties: tok must be a contiguous int64 tensor of B elements")
-    if row_state is not None and (row_state.dtype != torch.int32 or tuple(row_state.shape) != (B, 2) or not row_state.is_contiguous()):
-        raise ValueError("logit_penalties: row_state must be a contiguous int32 (B, 2) tensor (BatchRows.row_state)")
-    for t in (state.counts, tok, row_state):
-        if t is not None and t.device != logits.device:
-            raise ValueError(f"logit_penalties: logits on {logits.device}, state on {t.device}")
     if not logits.is_cuda:
         _logit_penalties_host(logits, state, None if tok is None else tok.view(-1), row_state)
         return logits
@@ -728,6 +738,15 @@ CONSTRAINT_SEQ_LEN_MAX = 16  # ids of one sequence, and the largest no-repeat n-
 
 def _is_seq(v) -> bool:
     return isinstance(v, (list, tuple))
+
+
+def per_row(name: str, v, batch: int, who: str = "constraints", what: str = "rows"):
+    """A scalar setting for every row, or one per row: a list of ``batch`` values (``who`` / ``what``: the caller's words in the error)."""
+    if _is_seq(v):
+        if len(v) != batch:
+            raise ValueError(f"{who}: {name} has {len(v)} entries for {batch} {what}")
+        return list(v)
+    return [v] * batch
 
 
 def _is_int(v) -> bool:
@@ -767,11 +786,7 @@ class ConstraintState:
     @staticmethod
     def per_row(name: str, v, batch: int):
         """A scalar setting for every row, or one per row."""
-        if _is_seq(v):
-            if len(v) != batch:
-                raise ValueError(f"constraints: {name} has {len(v)} entries for {batch} rows")
-            return list(v)
-        return [v] * batch
+        return per_row(name, v, batch)
 
     @staticmethod
     def per_row_sequences(name: str, v, batch: int):
@@ -941,24 +956,13 @@ def history_constraints(logits: Tensor, state: ConstraintState, tok: Tensor | No
     this step, appended first; None (the first token after a prefill): nothing is appended.  ``row_state`` / ``live`` (together or
     not at all): a ``BatchRows``' - finished rows are left untouched, and stop sequences are evaluated only with them.  Returns
     `logits`.  CPU tensors take the host form (Python, the same rules)."""
-    if logits.dim() != 2 or logits.shape[1] < 1 or logits.stride(1) != 1:
-        raise ValueError(f"history_constraints: logits must be (B, N) with N >= 1 and unit column stride, got {tuple(logits.shape)}")
-    B, N = logits.shape
-    if B != state.batch:
-        raise ValueError(f"history_constraints: {B} logits rows for a ConstraintState of {state.batch}")
-    if B > 1 and logits.stride(0) < N:
-        raise ValueError("history_constraints: overlapping logits rows")
-    if tok is not None and (tok.dtype != torch.int64 or tok.numel() != B or not tok.is_contiguous()):
-        raise ValueError("history_constraints: tok must be a contiguous int64 tensor of B elements")
     if (row_state is None) != (live is None):
         raise ValueError("history_constraints: row_state and live go together")
-    if row_state is not None and (row_state.dtype != torch.int32 or tuple(row_state.shape) != (B, 2) or not row_state.is_contiguous()):
-        raise ValueError("history_constraints: row_state must be a contiguous int32 (B, 2) tensor (BatchRows.row_state)")
+    B, N = _check_step_logits("history_constraints", logits, state.batch, tok, row_state, state.hist, "ConstraintState")
     if live is not None and (live.dtype != torch.int32 or live.numel() != 1):
         raise ValueError("history_constraints: live must be an int32 tensor of one element (BatchRows.live)")
-    for t in (state.hist, tok, row_state, live):
-        if t is not None and t.device != logits.device:
-            raise ValueError(f"history_constraints: logits on {logits.device}, state on {t.device}")
+    if live is not None and live.device != logits.device:
+        raise ValueError(f"history_constraints: logits on {logits.device}, state on {live.device}")
     if not logits.is_cuda:
         _history_constraints_host(logits, state, None if tok is None else tok.view(-1), row_state, live)
         return logits
@@ -980,19 +984,20 @@ GRAMMAR_CHUNK = 256          # tokens one workgroup of the launch walks (QL_GRAM
 GRAMMAR_DEAD = 0xFFFF
 
 
-class GrammarState:
-    """Static buffers of ``grammar_mask`` for a batch of rows (a captured step reads and updates them in place).  Per session: the
-    vocabulary's byte table ``tok_off`` (n_tok + 1,) int32 / ``tok_bytes`` uint8 (``grammar.TokenBytes``).  Per row: ``class_of``
-    (batch, 256) uint8, ``table`` (batch, GRAMMAR_TABLE_MAX) uint16 bit patterns (held as int16), ``accept`` (batch, GRAMMAR_STATES_MAX
-    + 1) uint8, ``cfg`` (batch, 2) int32 = n_states (0: the row has no grammar), eos_id (-1: none), ``state`` (batch,) int32 (-1 = dead)
-    and ``ticket`` (batch,) int32.  ``dfas``: what the last ``arm`` armed; ``active``: whether any row has a grammar."""
+class _AutomatonState:
+    """What ``GrammarState`` and ``PdaState`` share.  Per session: the vocabulary's byte table ``tok_off`` (n_tok + 1,) int32 / ``tok_bytes``
+    uint8 (``grammar.TokenBytes``).  Per row: ``class_of`` (batch, 256) uint8, ``table`` (batch, GRAMMAR_TABLE_MAX) uint16 bit patterns
+    (held as int16), ``accept`` (batch, GRAMMAR_STATES_MAX + 1) uint8, ``cfg`` (batch, n_cfg) int32 starting with n_states (0: the row has
+    no grammar), eos_id (-1: none), ``state`` (batch,) int32 (-1 = dead) and ``ticket`` (batch,) int32.  ``active``: whether any row has a
+    grammar."""
 
-    def __init__(self, batch: int, token_bytes, device):
+    def __init__(self, batch: int, token_bytes, device, n_cfg: int):
         from .grammar import TokenBytes
+        name = type(self).__name__
         if batch < 1:
-            raise ValueError(f"GrammarState: batch >= 1 (got {batch})")
+            raise ValueError(f"{name}: batch >= 1 (got {batch})")
         if not isinstance(token_bytes, TokenBytes):
-            raise ValueError("GrammarState: token_bytes must be a grammar.TokenBytes (grammar.token_byte_table builds one)")
+            raise ValueError(f"{name}: token_bytes must be a grammar.TokenBytes (grammar.token_byte_table builds one)")
         self.batch, self.device, self.token_bytes = batch, torch.device(device), token_bytes
         self.n_tok, self.n_bytes = len(token_bytes), int(token_bytes.bytes.size)
         self.tok_off = torch.from_numpy(token_bytes.off.copy()).to(device)
@@ -1000,11 +1005,58 @@ class GrammarState:
         self.class_of = torch.zeros((batch, 256), dtype=torch.uint8, device=device)
         self.table = torch.full((batch, GRAMMAR_TABLE_MAX), -1, dtype=torch.int16, device=device)
         self.accept = torch.zeros((batch, GRAMMAR_STATES_MAX + 1), dtype=torch.uint8, device=device)
-        self.cfg = torch.zeros((batch, 2), dtype=torch.int32, device=device)
+        self.cfg = torch.zeros((batch, n_cfg), dtype=torch.int32, device=device)
         self.state = torch.zeros(batch, dtype=torch.int32, device=device)
         self.ticket = torch.zeros(batch, dtype=torch.int32, device=device)
-        self.dfas = [None] * batch
         self.active = False
+
+    @staticmethod
+    def _check_eos(b: int, e, vocab: int | None) -> int:
+        """Row b's end id as an int, -1 for None."""
+        if e is None:
+            e = -1
+        if not _is_int(e) or not -1 <= int(e) < (2 ** 31 if vocab is None else vocab):
+            raise ValueError(f"grammar: row {b}: eos_id {e!r} outside the vocabulary")
+        return int(e)
+
+    def _arm_tables(self, automata, eos, cfg_tail=None):
+        """The common half of ``arm``: every row's tables and ``cfg`` (behind n_states and the end id: ``cfg_tail(automaton)``) stored,
+        every state and ticket back to 0."""
+        B = self.batch
+        class_of = np.zeros((B, 256), dtype=np.uint8)
+        table = np.full((B, GRAMMAR_TABLE_MAX), GRAMMAR_DEAD, dtype=np.uint16)
+        accept = np.zeros((B, GRAMMAR_STATES_MAX + 1), dtype=np.uint8)
+        cfg = np.zeros(tuple(self.cfg.shape), dtype=np.int32)
+        for b, d in enumerate(automata):
+            cfg[b, 1] = eos[b]
+            if d is None:
+                continue
+            cfg[b, 0] = d.n_states
+            if cfg_tail is not None:
+                cfg[b, 2:] = cfg_tail(d)
+            class_of[b] = d.class_of
+            table[b, :d.table.size] = d.table.reshape(-1)
+            accept[b, :d.n_states] = d.accept
+        self.class_of.copy_(torch.from_numpy(class_of))
+        self.table.copy_(torch.from_numpy(table.view(np.int16)))
+        self.accept.copy_(torch.from_numpy(accept))
+        self.cfg.copy_(torch.from_numpy(cfg))
+        self.state.zero_()
+        self.ticket.zero_()
+        self.active = any(d is not None for d in automata)
+
+    def states(self):
+        """Every row's current state, read back: a list of ints, -1 = dead."""
+        return self.state.cpu().tolist()
+
+
+class GrammarState(_AutomatonState):
+    """Static buffers of ``grammar_mask`` for a batch of rows (a captured step reads and updates them in place): ``_AutomatonState``'s, with
+    ``cfg`` (batch, 2) int32 = n_states, eos_id and the table indexed ``state * n_classes + class``.  ``dfas``: what the last ``arm`` armed."""
+
+    def __init__(self, batch: int, token_bytes, device):
+        super().__init__(batch, token_bytes, device, n_cfg=2)
+        self.dfas = [None] * batch
 
     @staticmethod
     def check(batch: int, dfas, eos_ids, vocab: int | None = None):
@@ -1015,58 +1067,30 @@ class GrammarState:
         eos = ConstraintState.per_row("eos_id", eos_ids, batch)
         out = []
         for b in range(batch):
-            d, e = dfas[b], eos[b]
+            d = dfas[b]
             if d is not None and not isinstance(d, ByteDFA):
                 raise ValueError(f"grammar: row {b}: a ByteDFA or None (got {type(d).__name__})")
             if d is not None and (d.n_states > GRAMMAR_STATES_MAX or d.n_states * d.n_classes > GRAMMAR_TABLE_MAX):
                 raise ValueError(f"grammar: row {b}: {d.n_states} states x {d.n_classes} byte classes outside the caps "
                                  f"({GRAMMAR_STATES_MAX} states, {GRAMMAR_TABLE_MAX} table entries)")
-            if e is None:
-                e = -1
-            if not _is_int(e) or not -1 <= int(e) < (2 ** 31 if vocab is None else vocab):
-                raise ValueError(f"grammar: row {b}: eos_id {e!r} outside the vocabulary")
-            out.append(int(e))
+            out.append(_AutomatonState._check_eos(b, eos[b], vocab))
         return dfas, out
 
     def arm(self, dfas, eos_ids=None):
         """Start a generation, in place (the buffers keep their addresses): row b follows ``dfas[b]`` (None: no grammar) from its start
         state, ``eos_ids[b]`` is the id allowed exactly in an accepting state.  Every state goes to 0, every ticket to 0."""
-        B = self.batch
-        dfas, eos = self.check(B, dfas, eos_ids)
-        class_of = np.zeros((B, 256), dtype=np.uint8)
-        table = np.full((B, GRAMMAR_TABLE_MAX), GRAMMAR_DEAD, dtype=np.uint16)
-        accept = np.zeros((B, GRAMMAR_STATES_MAX + 1), dtype=np.uint8)
-        cfg = np.zeros((B, 2), dtype=np.int32)
-        for b, d in enumerate(dfas):
-            cfg[b, 1] = eos[b]
-            if d is None:
-                continue
-            cfg[b, 0] = d.n_states
-            class_of[b] = d.class_of
-            table[b, :d.n_states * d.n_classes] = d.table.reshape(-1)
-            accept[b, :d.n_states] = d.accept
-        self.class_of.copy_(torch.from_numpy(class_of))
-        self.table.copy_(torch.from_numpy(table.view(np.int16)))
-        self.accept.copy_(torch.from_numpy(accept))
-        self.cfg.copy_(torch.from_numpy(cfg))
-        self.state.zero_()
-        self.ticket.zero_()
+        dfas, eos = self.check(self.batch, dfas, eos_ids)
+        self._arm_tables(dfas, eos)
         self.dfas = list(dfas)
-        self.active = any(d is not None for d in dfas)
         return self
-
-    def states(self):
-        """Every row's current state, read back: a list of ints, -1 = dead."""
-        return self.state.cpu().tolist()
 
     def tensors(self):
         """What a step changes and a capture saves and restores (the tickets are back at 0 behind every launch)."""
         return (self.state,)
 
 
-def _grammar_mask_host(logits: Tensor, state: GrammarState, tok, row_state):
-    """CPU form of qlinear_grammar_mask: rules 0 - 3 of its comment in include/qlinear_hip.h, row by row in Python."""
-    B, N = logits.shape
+def _host_token_bytes(state: _AutomatonState, N: int):
+    """``token(i)`` of the host forms: (id i's bytes, whether its offsets are sound) - an id outside the logits or the table has no bytes."""
     off, data = state.tok_off.numpy(), state.tok_bytes.numpy()
     n_tok, n_bytes = state.n_tok, state.n_bytes
 
@@ -1075,8 +1099,16 @@ def _grammar_mask_host(logits: Tensor, state: GrammarState, tok, row_state):
             return b"", True
         o0, o1 = int(off[i]), int(off[i + 1])
         if o0 < 0 or o1 < o0 or o1 > n_bytes:
-            return b"", False                                  # corrupt offsets: masked (the fed id: the state dies)
+            return b"", False                                  # corrupt offsets: masked (the fed id: the row dies)
         return data[o0:o1].tobytes(), True
+
+    return token
+
+
+def _grammar_mask_host(logits: Tensor, state: GrammarState, tok, row_state):
+    """CPU form of qlinear_grammar_mask: rules 0 - 3 of its comment in include/qlinear_hip.h, row by row in Python."""
+    B, N = logits.shape
+    token = _host_token_bytes(state, N)
 
     for b in range(B):
         if row_state is not None and int(row_state[b, 1]) & BatchRows.FINISHED:
@@ -1125,20 +1157,7 @@ def grammar_mask(logits: Tensor, state: GrammarState, tok: Tensor | None = None,
     untouched.  Returns `logits`.  CPU tensors take the host form (Python, the same rules)."""
     if not isinstance(state, GrammarState):
         raise ValueError("grammar_mask: state must be a GrammarState")
-    if logits.dim() != 2 or logits.shape[1] < 1 or logits.stride(1) != 1:
-        raise ValueError(f"grammar_mask: logits must be (B, N) with N >= 1 and unit column stride, got {tuple(logits.shape)}")
-    B, N = logits.shape
-    if B != state.batch:
-        raise ValueError(f"grammar_mask: {B} logits rows for a GrammarState of {state.batch}")
-    if B > 1 and logits.stride(0) < N:
-        raise ValueError("grammar_mask: overlapping logits rows")
-    if tok is not None and (tok.dtype != torch.int64 or tok.numel() != B or not tok.is_contiguous()):
-        raise ValueError("grammar_mask: tok must be a contiguous int64 tensor of B elements")
-    if row_state is not None and (row_state.dtype != torch.int32 or tuple(row_state.shape) != (B, 2) or not row_state.is_contiguous()):
-        raise ValueError("grammar_mask: row_state must be a contiguous int32 (B, 2) tensor (BatchRows.row_state)")
-    for t in (state.state, tok, row_state):
-        if t is not None and t.device != logits.device:
-            raise ValueError(f"grammar_mask: logits on {logits.device}, state on {t.device}")
+    B, N = _check_step_logits("grammar_mask", logits, state.batch, tok, row_state, state.state, "GrammarState")
     if not logits.is_cuda:
         _grammar_mask_host(logits, state, None if tok is None else tok.view(-1), row_state)
         return logits
@@ -1159,33 +1178,17 @@ PDA_LOCAL_MAX = 32           # symbols one token's walk may hold above the lowes
 PDA_SYMS_MAX = 3             # stack symbols 1..n_syms (QL_PDA_SYMS_MAX)
 
 
-class PdaState:
-    """Static buffers of ``pda_mask`` for a batch of rows (a captured step reads and updates them in place).  The vocabulary's byte table
-    and ``class_of`` / ``table`` / ``accept`` / ``ticket`` are ``GrammarState``'s (the table indexed ``(state * (n_syms + 1) + top) *
-    n_classes + class``, entries as ``grammar.pda_entry`` packs them).  Per row besides: ``cfg`` (batch, 4) int32 = n_states (0: the row
-    has no grammar), eos_id (-1: none), n_syms, max_depth; ``state`` (batch,) int32 (-1 = dead); ``depth`` (batch,) int32; ``stack``
-    (batch, PDA_DEPTH_MAX) uint8, bottom first.  ``pdas``: what the last ``arm`` armed; ``active``: whether any row has a grammar."""
+class PdaState(_AutomatonState):
+    """Static buffers of ``pda_mask`` for a batch of rows (a captured step reads and updates them in place): ``_AutomatonState``'s (the
+    table indexed ``(state * (n_syms + 1) + top) * n_classes + class``, entries as ``grammar.pda_entry`` packs them), with ``cfg`` (batch, 4)
+    int32 = n_states, eos_id, n_syms, max_depth, and per row besides ``depth`` (batch,) int32 and ``stack`` (batch, PDA_DEPTH_MAX) uint8,
+    bottom first.  ``pdas``: what the last ``arm`` armed."""
 
     def __init__(self, batch: int, token_bytes, device):
-        from .grammar import TokenBytes
-        if batch < 1:
-            raise ValueError(f"PdaState: batch >= 1 (got {batch})")
-        if not isinstance(token_bytes, TokenBytes):
-            raise ValueError("PdaState: token_bytes must be a grammar.TokenBytes (grammar.token_byte_table builds one)")
-        self.batch, self.device, self.token_bytes = batch, torch.device(device), token_bytes
-        self.n_tok, self.n_bytes = len(token_bytes), int(token_bytes.bytes.size)
-        self.tok_off = torch.from_numpy(token_bytes.off.copy()).to(device)
-        self.tok_bytes = torch.from_numpy(token_bytes.bytes.copy() if self.n_bytes else np.zeros(1, dtype=np.uint8)).to(device)
-        self.class_of = torch.zeros((batch, 256), dtype=torch.uint8, device=device)
-        self.table = torch.full((batch, GRAMMAR_TABLE_MAX), -1, dtype=torch.int16, device=device)
-        self.accept = torch.zeros((batch, GRAMMAR_STATES_MAX + 1), dtype=torch.uint8, device=device)
-        self.cfg = torch.zeros((batch, 4), dtype=torch.int32, device=device)
-        self.state = torch.zeros(batch, dtype=torch.int32, device=device)
+        super().__init__(batch, token_bytes, device, n_cfg=4)
         self.depth = torch.zeros(batch, dtype=torch.int32, device=device)
         self.stack = torch.zeros((batch, PDA_DEPTH_MAX), dtype=torch.uint8, device=device)
-        self.ticket = torch.zeros(batch, dtype=torch.int32, device=device)
         self.pdas = [None] * batch
-        self.active = False
 
     @staticmethod
     def check(batch: int, pdas, eos_ids, vocab: int | None = None):
@@ -1196,7 +1199,7 @@ class PdaState:
         eos = ConstraintState.per_row("eos_id", eos_ids, batch)
         out_p, out_e, lifted = [], [], {}
         for b in range(batch):
-            d, e = pdas[b], eos[b]
+            d = pdas[b]
             if isinstance(d, ByteDFA):
                 d = lifted[id(d)] if id(d) in lifted else lifted.setdefault(id(d), BytePDA.from_dfa(d))
             if d is not None and not isinstance(d, BytePDA):
@@ -1206,47 +1209,20 @@ class PdaState:
                 raise ValueError(f"grammar: row {b}: {d.n_states} states x {d.n_syms + 1} stack tops x {d.n_classes} byte classes, depth "
                                  f"{d.max_depth} outside the caps ({GRAMMAR_STATES_MAX} states, {GRAMMAR_TABLE_MAX} table entries, "
                                  f"{PDA_SYMS_MAX} symbols, depth {PDA_DEPTH_MAX})")
-            if e is None:
-                e = -1
-            if not _is_int(e) or not -1 <= int(e) < (2 ** 31 if vocab is None else vocab):
-                raise ValueError(f"grammar: row {b}: eos_id {e!r} outside the vocabulary")
             out_p.append(d)
-            out_e.append(int(e))
+            out_e.append(_AutomatonState._check_eos(b, eos[b], vocab))
         return out_p, out_e
 
     def arm(self, pdas, eos_ids=None):
         """Start a generation, in place (the buffers keep their addresses): row b follows ``pdas[b]`` (None: no grammar) from its start
         configuration - state 0, an empty stack - and ``eos_ids[b]`` is the id allowed exactly in an accepting state with an empty
         stack.  Every ticket goes to 0."""
-        B = self.batch
-        pdas, eos = self.check(B, pdas, eos_ids)
-        class_of = np.zeros((B, 256), dtype=np.uint8)
-        table = np.full((B, GRAMMAR_TABLE_MAX), GRAMMAR_DEAD, dtype=np.uint16)
-        accept = np.zeros((B, GRAMMAR_STATES_MAX + 1), dtype=np.uint8)
-        cfg = np.zeros((B, 4), dtype=np.int32)
-        for b, d in enumerate(pdas):
-            cfg[b, 1] = eos[b]
-            if d is None:
-                continue
-            cfg[b, 0], cfg[b, 2], cfg[b, 3] = d.n_states, d.n_syms, d.max_depth
-            class_of[b] = d.class_of
-            table[b, :d.table.size] = d.table.reshape(-1)
-            accept[b, :d.n_states] = d.accept
-        self.class_of.copy_(torch.from_numpy(class_of))
-        self.table.copy_(torch.from_numpy(table.view(np.int16)))
-        self.accept.copy_(torch.from_numpy(accept))
-        self.cfg.copy_(torch.from_numpy(cfg))
-        self.state.zero_()
+        pdas, eos = self.check(self.batch, pdas, eos_ids)
+        self._arm_tables(pdas, eos, lambda d: (d.n_syms, d.max_depth))
         self.depth.zero_()
         self.stack.zero_()
-        self.ticket.zero_()
         self.pdas = list(pdas)
-        self.active = any(d is not None for d in pdas)
         return self
-
-    def states(self):
-        """Every row's current state, read back: a list of ints, -1 = dead."""
-        return self.state.cpu().tolist()
 
     def configs(self):
         """Every row's configuration, read back: (state, tuple of symbols), or None for a dead row."""
@@ -1261,16 +1237,7 @@ class PdaState:
 def _pda_mask_host(logits: Tensor, state: PdaState, tok, row_state):
     """CPU form of qlinear_pda_mask: rules 0 - 6 of its comment in include/qlinear_hip.h, row by row in Python."""
     B, N = logits.shape
-    off, data = state.tok_off.numpy(), state.tok_bytes.numpy()
-    n_tok, n_bytes = state.n_tok, state.n_bytes
-
-    def token(i):
-        if not 0 <= i < min(N, n_tok):
-            return b"", True
-        o0, o1 = int(off[i]), int(off[i + 1])
-        if o0 < 0 or o1 < o0 or o1 > n_bytes:
-            return b"", False                                  # corrupt offsets: masked (the fed id: the row dies)
-        return data[o0:o1].tobytes(), True
+    token = _host_token_bytes(state, N)
 
     for b in range(B):
         if row_state is not None and int(row_state[b, 1]) & BatchRows.FINISHED:
@@ -1349,20 +1316,7 @@ def pda_mask(logits: Tensor, state: PdaState, tok: Tensor | None = None, row_sta
     finished rows are left untouched.  Returns `logits`.  CPU tensors take the host form (Python, the same rules)."""
     if not isinstance(state, PdaState):
         raise ValueError("pda_mask: state must be a PdaState")
-    if logits.dim() != 2 or logits.shape[1] < 1 or logits.stride(1) != 1:
-        raise ValueError(f"pda_mask: logits must be (B, N) with N >= 1 and unit column stride, got {tuple(logits.shape)}")
-    B, N = logits.shape
-    if B != state.batch:
-        raise ValueError(f"pda_mask: {B} logits rows for a PdaState of {state.batch}")
-    if B > 1 and logits.stride(0) < N:
-        raise ValueError("pda_mask: overlapping logits rows")
-    if tok is not None and (tok.dtype != torch.int64 or tok.numel() != B or not tok.is_contiguous()):
-        raise ValueError("pda_mask: tok must be a contiguous int64 tensor of B elements")
-    if row_state is not None and (row_state.dtype != torch.int32 or tuple(row_state.shape) != (B, 2) or not row_state.is_contiguous()):
-        raise ValueError("pda_mask: row_state must be a contiguous int32 (B, 2) tensor (BatchRows.row_state)")
-    for t in (state.state, tok, row_state):
-        if t is not None and t.device != logits.device:
-            raise ValueError(f"pda_mask: logits on {logits.device}, state on {t.device}")
+    B, N = _check_step_logits("pda_mask", logits, state.batch, tok, row_state, state.state, "PdaState")
     if not logits.is_cuda:
         _pda_mask_host(logits, state, None if tok is None else tok.view(-1), row_state)
         return logits

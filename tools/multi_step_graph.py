@@ -4,7 +4,7 @@ import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench_extras
-from chatglm_q_amd.decoder import DecodeSession
+from chatglm_q_amd.decoder import DecodeSession, step_plan
 
 dev = torch.device("cuda:0")
 model, cfg = bench_extras._chatglm2_6b(torch, dev, torch.float16)
@@ -17,7 +17,7 @@ for N in (1, 2, 4, 8):
     saved = (sess.tok.clone(), sess.write_index.clone(), sess.pos.clone(), sess.mask.clone())
     with torch.cuda.graph(g):
         for _ in range(N):
-            sess._step_body(True)
+            sess._step_body(step_plan(greedy=True))
     for dst, src in zip((sess.tok, sess.write_index, sess.pos, sess.mask), saved):
         dst.copy_(src)
     reps = 128 // N
